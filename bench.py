@@ -6,17 +6,24 @@ DA head only, 1 source + 1 target image of 1024 x 2048 per GPU per step (SOLVER.
 256 ROIs sampled per image, SGD(momentum) step included.  One "step" = forward + backward (+ bucketed gradient
 all-reduce when n_gpus > 1) + fused SGD over one such batch; inputs are resident in HBM before the timed region.
 Weak scaling: every rank processes its own (source, target) pair.
-Work the recipe never reads is not evaluated (DESIGN.md section 4 "Unread work"; the line's `elided` list says what,
-`flop_per_step` says how many algorithmic FLOPs a step executes, `step_frac` = flop_per_step / time / ceiling).  After
-the headline loop the other BASELINE recipes (configs[2] `da`, configs[3] `triplet`, configs[4] `fpn_dcn_da`: R-101-FPN +
-DCN) are timed for a few steps each, every one in a process of its own, and reported under `other_workloads`; `resolutions`
-holds `img_only` and `da` at the reference yaml's own training size (INPUT.MIN/MAX_SIZE_TRAIN 600 / 1200 -> 608 x 1216
-padded).  With N > 1 ranks the line carries `comm` (bucket count, all-reduce time, exposed wait in finalize()).
+Work the recipe never reads is not evaluated (DESIGN.md section 4 "Unread work"; the line's `elided` list says what).
 
-Launch:  python bench.py --gpus 1 --steps K --warmup W
+A plain run sets up, tunes the schedule, warms up, times the K steps and prints the line (metric / value / ms_per_step
+...); `--dump-outputs DIR` then also writes what the last timed step computed (DIR/<name>.npy: see dump_outputs()),
+which for that run starts from the seeded parameters and a fresh optimizer state (reset outside the timed interval), so
+that two runs with the same arguments write the same outputs to rounding.
+Everything else is measured with `--full` only: the dominant GEMM family bracketed with HIP events in the timed region
+(`roofline`, `kernel_timing`), untimed extra passes with every GEMM bracketed (`flop_per_step`, `step_frac` =
+flop_per_step / time / ceiling, `roofline.families`), the same loop on one GEMM stream (`one_stream`), the CPU oracle's
+step (`cpu_baseline`), the other BASELINE recipes (configs[2] `da`, configs[3] `triplet`, configs[4] `fpn_dcn_da`:
+R-101-FPN + DCN) timed for a few steps each, every one in a process of its own (`other_workloads`), `resolutions`:
+`img_only` and `da` at the reference yaml's own training size (INPUT.MIN/MAX_SIZE_TRAIN 600 / 1200 -> 608 x 1216 padded),
+and with N > 1 ranks `comm` (bucket count, all-reduce time, exposed wait in finalize()) and the ranks' parameter check.
+
+Launch:  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line (metric / value / roofline / cpu_baseline ...).
+Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -65,6 +72,39 @@ WORKLOADS = {
     "fpn_dcn_da": ("configs/da_faster_rcnn/e2e_da_faster_rcnn_R_101_FPN_DCN_cityscapes_to_foggy_cityscapes.yaml", [],
                    2, "R-101-FPN + DCN (res3-5) + DA heads over the pyramid, 1 source + 1 target"),
 }
+
+
+# --dump-outputs: elements drawn (with replacement, duplicates dropped) from the trainable parameters after the last step
+PARAM_SAMPLE = 1 << 20
+
+
+def reset_training_state(model, opt, start, device):
+    """parameters back to the values `start` holds, momentum buffers back to zero (what a fresh optimizer starts from),
+    and the cached derived forms of the weights invalidated, as after any weight write outside the optimizer"""
+    from da_detect_amd import _C
+
+    with torch.no_grad():
+        for p, s in zip([p for p in model.parameters() if p.requires_grad], start):
+            p.copy_(s)
+            buf = opt.state[p].get("momentum_buffer")
+            if buf is not None:
+                buf.zero_()
+    _C.bump_weight_epoch(device, trained_only=True)
+
+
+def dump_outputs(out_dir, model, loss_dict):
+    """what the timed path hands its caller after its last step: every loss as DIR/<loss name>.npy (float32 scalar) and
+    the parameters the SGD step left as DIR/params_sample.npy — a fixed seeded sample of the elements of the trainable
+    parameters (float32, in parameters() order, logical element order whatever the memory format)"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in loss_dict.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(float(v.detach()), dtype=np.float32))
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters() if p.requires_grad])
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), PARAM_SAMPLE))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, "params_sample.npy"), sample)
 
 
 def benchmark_init(model, seed):
@@ -234,9 +274,9 @@ def elided_work(c, model, targets):
 
 
 def run_workload(args, name, device, rank, world, steps, warmup, headline):
-    """build the recipe, tune the schedule, warm up, time `steps` steps between barriers.  headline: with the dominant
-    kernel bracketed in the timed region; always followed by an UNTIMED pass with every GEMM bracketed (single process
-    only), from which flop_per_step and the all-GEMM rate come."""
+    """build the recipe, tune the schedule, warm up, time `steps` steps between barriers.  With --full: headline with the
+    dominant kernel bracketed in the timed region; always followed by an UNTIMED pass with every GEMM bracketed (single
+    process only), from which flop_per_step and the all-GEMM rate come."""
     from da_detect_amd import _C
     from da_detect_amd.data.synthetic import make_batch
     from da_detect_amd.utils import streams
@@ -245,6 +285,10 @@ def run_workload(args, name, device, rank, world, steps, warmup, headline):
     yaml_path, overrides, images_per_gpu, workload_desc = WORKLOADS[name]
     height, width = (HEIGHT, WIDTH) if args.image_hw is None else [int(v) for v in args.image_hw.lower().split("x")]
     c, model, opt, reducer = build(yaml_path, device, seed=100, overrides=overrides)
+    # --dump-outputs: the last timed step starts again from the seeded parameters.  The step's float-atomic sums differ in
+    # the last bit from run to run, and tens of SGD steps on one fixed batch grow that into visible differences; from the
+    # seeded state what the step computes depends on the arguments alone, to rounding
+    start = [p.detach().clone() for p in model.parameters() if p.requires_grad] if headline and args.dump_outputs else None
     enable_overlapped_rpn_backward(model, not args.no_overlap)
     images, targets = make_batch(c, images_per_gpu, height, width, seed=100 + rank, device=device)
 
@@ -264,10 +308,10 @@ def run_workload(args, name, device, rank, world, steps, warmup, headline):
         tuner.step_end()
     for _ in range(warmup):
         loss_dict = train_step(model, opt, images, targets)
-    if world > 1:
+    if world > 1 and args.full:
         reducer.record_comm(True)
     profiler = None
-    if headline and not args.no_kernel_timing and rank == 0:
+    if headline and args.full and not args.no_kernel_timing and rank == 0:
         # timed region: only the dominant kernel family (128x128-tile forward / data-gradient GEMM) is bracketed —
         # every event pair between two launches costs dispatch concurrency (measured: ~1 ms / step for all GEMMs)
         # (round 5: the 256 x 256-tile forward / data-gradient kernel, csrc/conv_big.hip, is the family with the most time)
@@ -275,18 +319,30 @@ def run_workload(args, name, device, rank, world, steps, warmup, headline):
     barrier()
     mem0 = torch.cuda.memory_stats(device) if os.environ.get("DADET_BENCH_MEMSTATS") else None
     t0 = time.perf_counter()
+    elapsed = 0.0
     for i in range(steps):
+        if start is not None and i == steps - 1:
+            # outside the timed interval (every rank resets, so the ranks stay identical)
+            barrier()
+            elapsed += time.perf_counter() - t0
+            reset_training_state(model, opt, start, device)
+            start = None
+            barrier()
+            t0 = time.perf_counter()
         # the brackets are not free (event pairs between launches cost dispatch concurrency: ~3% of the step when every
         # step is bracketed), so only every `--kernel-timing-every`-th timed step carries them
         _C.PROFILER = profiler if (profiler is not None and i % args.kernel_timing_every == 0) else None
         loss_dict = train_step(model, opt, images, targets)
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     _C.PROFILER = None
-    comm = reducer.comm_summary() if world > 1 else None
+    if headline and args.dump_outputs and rank == 0:
+        # before anything below runs further steps on the same parameters
+        dump_outputs(args.dump_outputs, model, loss_dict)
+    comm = reducer.comm_summary() if world > 1 and args.full else None
     reducer.record_comm(False)
     one_stream = None
-    if headline and world == 1 and streams.lane_in_use() and not args.no_kernel_timing:
+    if headline and args.full and world == 1 and streams.lane_in_use() and not args.no_kernel_timing:
         # the same loop with the second GEMM stream off, so that a scaling curve whose N > 1 points kept one stream can be
         # read against a like-for-like N = 1 point
         saved = (streams.WGRAD_OVERLAP, streams.WGRAD_LANE_ROWS)
@@ -309,7 +365,7 @@ def run_workload(args, name, device, rank, world, steps, warmup, headline):
             file=sys.stderr)
     exclusive = everything = None
     extra = extra_elapsed = 0
-    if not args.no_kernel_timing and rank == 0 and world == 1:
+    if args.full and not args.no_kernel_timing and rank == 0 and world == 1:
         # extra UNTIMED passes (single process only: a lone rank must not enter the gradient all-reduce):
         # (1) all GEMM kernels bracketed, same schedule -> which kernel dominates, union-of-busy rate, FLOPs per step;
         # (2) headline only: the same kernels without a second GEMM stream beside them -> per-kernel durations that do
@@ -339,7 +395,7 @@ def run_workload(args, name, device, rank, world, steps, warmup, headline):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ranks_in_sync = None
-    if world > 1:
+    if world > 1 and args.full:
         # data-parallel invariant, checked after the timed region: every rank applied the same averaged gradients to
         # the same parameters, so the parameters are still identical bit for bit
         chk = torch.stack([p.detach().double().sum() for p in model.parameters()])
@@ -367,7 +423,7 @@ def other_in_subprocess(args, name, image_hw=None):
     -> the child's line reduced to the `other_workloads` record (None if the child failed: stderr says why)"""
     import subprocess
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", name, "--others", "none",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", "1", "--workload", name, "--others", "none",
            "--steps", str(args.other_steps), "--warmup", str(max(3, args.warmup // 2)), "--no-cpu-baseline",
            "--gemm-mode", str(args.gemm_mode)]
     if image_hw is not None:
@@ -392,7 +448,7 @@ def other_in_subprocess(args, name, image_hw=None):
            "image_hw": cfg_.get("image_hw"),
            "steps": line["steps"], "ms_per_step": line["ms_per_step"], "images_per_s": line["value"],
            "schedule": cfg_.get("schedule"), "elided": line.get("elided"), "process": "its own (python bench.py "
-           "--workload %s --others none --steps %d --warmup %d%s)" % (
+           "--full --workload %s --others none --steps %d --warmup %d%s)" % (
                name, line["steps"], line["warmup"], "" if image_hw is None else " --image-hw " + image_hw)}
     if line.get("flop_per_step") is not None:
         rec["flop_per_step"] = line["flop_per_step"]
@@ -407,19 +463,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)   # steady state after >= 10 warm-up iterations
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel timing and roofline, one-stream "
+                         "loop, CPU baseline, other recipes and resolutions, the N > 1 comm block and parameter check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses and a seeded sample of the parameters after the last timed step as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="(--full) leave out every kernel-timing pass")
     ap.add_argument("--kernel-timing-every", type=int, default=4,
-                    help="bracket the dominant kernel's launches with HIP events in every N-th timed step")
+                    help="(--full) bracket the dominant kernel's launches with HIP events in every N-th timed step")
     ap.add_argument("--workload", default="img_only", choices=sorted(WORKLOADS),
                     help="img_only (default, BASELINE configs[1]) | da (configs[2]) | triplet (configs[3]) | "
                          "triplet_aligned | fpn_dcn_da (configs[4]); non-default workloads are extra measurements")
     ap.add_argument("--others", default=None,
-                    help="comma-separated workloads timed after the headline loop and reported under other_workloads "
+                    help="(--full) comma-separated workloads timed after the headline loop and reported under other_workloads "
                          "(default: da,triplet,fpn_dcn_da next to the default headline, none otherwise; 'none' switches "
                          "it off)")
     ap.add_argument("--resolutions", default=None,
-                    help="HxW at which img_only and da are timed again and reported under `resolutions` (default: 608x1216, "
+                    help="(--full) HxW at which img_only and da are timed again and reported under `resolutions` (default: 608x1216, "
                          "the reference yaml's own training size, next to the default headline; 'none' switches it off)")
     ap.add_argument("--other-steps", type=int, default=10)
     ap.add_argument("--image-hw", default=None, help="HxW of the synthetic images (default 1024x2048)")
@@ -428,6 +489,10 @@ def main():
                     help="3: fp32 operands as 3 bf16 terms, 6 bf16 MFMAs per K=16 (fp32-class accuracy, default); "
                          "0: exact fp32 MFMA; 2: 2-term split (~2^-16 products)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and any(v not in (None, "none") for v in (args.others, args.resolutions)):
+        ap.error("--others / --resolutions are measured with --full only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (what torch.distributed.run would do)
@@ -461,7 +526,9 @@ def main():
     peak = FP32_MFMA_PEAK_TFLOPS if args.gemm_mode == 0 else BF16_MFMA_PEAK_TFLOPS / mfma_per_product
 
     r = run_workload(args, args.workload, device, rank, world, args.steps, args.warmup, headline=True)
-    if args.others is None:
+    if not args.full:
+        others = []
+    elif args.others is None:
         # N > 1 (the driver's scaling runs): the headline recipe only — the other recipes would be built as further models
         # of every rank's process, and a failure of one of them on one rank would leave the others waiting in a collective
         # with the headline line unprinted; `--others da,triplet,fpn_dcn_da` asks for them explicitly
@@ -506,6 +573,8 @@ def main():
     default_run = args.workload == "img_only" and args.image_hw is None
     # (an explicit --others, e.g. the profiling scripts' `--others none`, also switches the default resolutions pass off)
     res_hw = ("608x1216" if (default_run and args.others is None) else "none") if args.resolutions is None else args.resolutions
+    if not args.full:
+        res_hw = "none"
     if res_hw != "none" and world == 1 and isolate:
         # SURVEY.md 8(d) "report both": the shipped yaml resizes Cityscapes to 600 x 1200 (608 x 1216 after padding to /32)
         for name in ("img_only", "da"):
@@ -629,7 +698,7 @@ def main():
                     roofline["gemm_streams"]["exclusive_tflops"] = roofline["achieved"]
                     roofline["gemm_streams"]["exclusive_frac"] = roofline["frac"]
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(YAML, seed=100) if args.workload == "img_only" and args.image_hw is None else None
                 if cpu is not None:
@@ -656,11 +725,12 @@ def main():
                        "image_hw": [height, width],
                        "parallelism": "dp%d" % world, "schedule": r["schedule"]},
             "elided": r["elided"],
-            "roofline": roofline, "cpu_baseline": cpu,
-            "other_workloads": other_results,
-            "resolutions": resolutions,
-            "kernel_timing": {k: {"launches": v["launches"], "total_ms": round(v["total_ms"], 3),
-                                  "tflops": round(v["achieved"] / 1e12, 2)} for k, v in kernels.items()},
+            **({"roofline": roofline, "cpu_baseline": cpu,
+                "other_workloads": other_results,
+                "resolutions": resolutions,
+                "kernel_timing": {k: {"launches": v["launches"], "total_ms": round(v["total_ms"], 3),
+                                      "tflops": round(v["achieved"] / 1e12, 2)} for k, v in kernels.items()}}
+               if args.full else {}),
             "final_losses": {k: round(v, 5) for k, v in r["losses"].items()},
         }
         if r["flop_per_step"] is not None:
@@ -681,7 +751,7 @@ def main():
                                   "note": "the same timed loop with the second GEMM stream off — the schedule an N > 1 "
                                           "run uses when its ranks' agreed tuner (or DADET_TUNE_SCHEDULE_RANKS=0) keeps "
                                           "one stream: config.schedule of that run says which; compare like with like"}
-        elif world == 1:
+        elif world == 1 and args.full:
             line["one_stream"] = {"ms_per_step": round(ms_per_step, 3), "value": round(value, 3), "unit": "images/s",
                                   "note": "the headline run already used one GEMM stream"}
         if r["comm"] is not None:

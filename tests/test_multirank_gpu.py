@@ -273,7 +273,8 @@ def test_bench_py_with_two_ranks_prints_one_line_with_its_comm_block(device):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DADET_BENCH_SHARE_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2",
+                        "--warmup", "1",
                         "--others", "none", "--no-cpu-baseline", "--image-hw", "512x1024"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]

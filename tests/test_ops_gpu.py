@@ -1228,31 +1228,27 @@ def test_stream_k_tail_matches_the_plain_grid(device, shape, monkeypatch):
 
 def test_hip_ops_against_the_reference_build_itself(device):
     """The reference's OWN compiled CPU operators (oracle/_ref/ref_C.so, built from maskrcnn_benchmark/csrc/{vision.cpp,
-    cpu/*.cpp} by oracle/build_ref.py; the binary travels to the GPU box, the sources do not) called on the same inputs
-    as the HIP operators: NMS kept indices identical (CPU tie rule), ROIAlign forward bit-exact — no restatement in
-    between."""
+    cpu/*.cpp} by oracle/build_ref.py) against the HIP operators on the same inputs: NMS kept indices identical (CPU tie
+    rule), ROIAlign forward bit-exact — no restatement in between.  The reference's outputs are stored in
+    tests/golden/ref_build_outputs.npz (golden/make_ref_build_outputs.py; ROIAlign outputs as SHA-256 digests of their
+    bytes), the inputs are regenerated from a seed and checked against the digests of the inputs the reference saw."""
     from da_detect_amd import _C
-    from oracle import build_ref
+    from golden.make_ref_build_outputs import gpu_cases, sha256
 
-    ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref/ref_C.so was not built (needs /root/reference at build time)")
-    g = torch.Generator().manual_seed(21)
-    for n in (1, 37, 2000, 12000):
-        xy = torch.rand((n, 2), generator=g) * torch.tensor([1900.0, 950.0])
-        boxes = torch.cat([xy, xy + torch.rand((n, 2), generator=g) * 250 + 2], 1)
-        scores = torch.rand(n, generator=g)
-        want = ref.nms(boxes, scores, 0.7)
-        keep, cnt = _C.nms_with_count(boxes.to(device), scores.to(device), 0.7, tie_rule=0)
-        assert torch.equal(keep[: int(cnt)].cpu(), want), "n=%d: NMS indices differ from the reference build" % n
-    for (C, H, W, R, ph, sr) in [(32, 24, 40, 50, 7, 2), (64, 64, 128, 128, 14, 0), (8, 13, 21, 20, 14, 0)]:
-        x = torch.randn((2, C, H, W), generator=g)
-        xy = torch.rand((R, 2), generator=g) * torch.tensor([W * 14.0, H * 14.0])
-        rois = torch.cat([torch.randint(0, 2, (R, 1), generator=g).float(), xy,
-                          xy + torch.rand((R, 2), generator=g) ** 2 * 400 + 1], 1)
-        want = ref.roi_align_forward(x, rois, 1 / 16.0, ph, ph, sr)
-        got = _C.roi_align_forward(x.to(device), rois.to(device), 1 / 16.0, ph, ph, sr)
-        assert torch.equal(got.cpu(), want), "ROIAlign forward differs from the reference build"
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_build_outputs.npz"))
+    nms, roi = gpu_cases()
+    for n, boxes, scores in nms:
+        assert sha256(boxes, scores) == str(z["gpu/nms_inputs_sha256_%d" % n]), "n=%d: not the fixture's inputs" % n
+        keep, cnt = _C.nms_with_count(torch.from_numpy(boxes).to(device), torch.from_numpy(scores).to(device), 0.7,
+                                      tie_rule=0)
+        assert np.array_equal(keep[: int(cnt)].cpu().numpy(), z["gpu/nms_keep_%d" % n]), \
+            "n=%d: NMS indices differ from the reference build" % n
+    for i, ((C, H, W, R, ph, sr), x, rois) in enumerate(roi):
+        assert sha256(x, rois) == str(z["gpu/roi_inputs_sha256_%d" % i]), "ROIAlign case %d: not the fixture's inputs" % i
+        xd, rd = torch.from_numpy(x).to(device), torch.from_numpy(rois).to(device)
+        got = _C.roi_align_forward(xd, rd, 1 / 16.0, ph, ph, sr)
+        assert sha256(got.cpu().numpy()) == str(z["gpu/roi_out_sha256_%d" % i]), \
+            "ROIAlign case %d: forward differs from the reference build" % i
 
 
 @pytest.mark.parametrize("shape", [

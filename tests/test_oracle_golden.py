@@ -45,22 +45,20 @@ def test_ops_match_reference_build_fixture():
 
 
 def test_ops_match_live_reference_build():
+    """the reference build's outputs are stored (tests/golden/ref_build_outputs.npz, written by
+    golden/make_ref_build_outputs.py); where oracle/_ref exists the live build must still produce them"""
     from oracle import build_ref
     from oracle import ops as O
 
+    z = np.load(os.path.join(GOLD, "ref_build_outputs.npz"))
+    x, rois, boxes, scores = z["cpu/x"], z["cpu/rois"], z["cpu/boxes"], z["cpu/scores"]
     ref = build_ref.load()
-    if ref is None:
-        pytest.skip("oracle/_ref/ref_C.so not built")
-    rng = np.random.default_rng(7)
-    x = rng.standard_normal((2, 6, 17, 23)).astype(np.float32)
-    rois = np.concatenate([rng.integers(0, 2, (30, 1)), rng.uniform(-10, 200, (30, 2)),
-                           rng.uniform(150, 420, (30, 2))], 1).astype(np.float32)
-    want = ref.roi_align_forward(torch.from_numpy(x), torch.from_numpy(rois), 1 / 16.0, 7, 7, 0).numpy()
-    assert np.array_equal(O.roi_align_forward(x, rois, 1 / 16.0, 7, 7, 0), want)
-    boxes = np.concatenate([rng.uniform(0, 300, (800, 2)), rng.uniform(300, 500, (800, 2))], 1).astype(np.float32)
-    scores = (rng.permutation(800) / 800.0).astype(np.float32)
-    assert np.array_equal(O.nms(boxes, scores, 0.6, 0),
-                          ref.nms(torch.from_numpy(boxes), torch.from_numpy(scores), 0.6).numpy())
+    if ref is not None:
+        want = ref.roi_align_forward(torch.from_numpy(x), torch.from_numpy(rois), 1 / 16.0, 7, 7, 0).numpy()
+        assert np.array_equal(want, z["cpu/roi_out"])
+        assert np.array_equal(ref.nms(torch.from_numpy(boxes), torch.from_numpy(scores), 0.6).numpy(), z["cpu/keep"])
+    assert np.array_equal(O.roi_align_forward(x, rois, 1 / 16.0, 7, 7, 0), z["cpu/roi_out"])
+    assert np.array_equal(O.nms(boxes, scores, 0.6, 0), z["cpu/keep"])
 
 
 def test_roi_align_backward_is_adjoint_of_forward():

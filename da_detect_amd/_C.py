@@ -802,6 +802,26 @@ def maxpool3x3s2(x):
     return _amax.carry(y, x)
 
 
+def maxpool3x3s2_relu_backward(y, gp, scale=None):
+    """backward of maxpool3x3s2 through the ReLU and the FrozenBN scale in front of it: y [N,C,H,W] the activation that
+    was pooled (>= 0), gp the gradient of the pooled map -> the gradient of the convolution output,
+    (y > 0 ? gp routed to each window's first maximum : 0) * scale[c]  (dadet_maxpool3x3s2_relu_backward)"""
+    _dev(y, "y"), _dev(gp, "gp")
+    y, gp = _nhwc(y), _nhwc(gp)
+    N, C, H, W = y.shape
+    Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+    assert tuple(gp.shape) == (N, C, Ho, Wo), "maxpool3x3s2_relu_backward: gp %s for y %s" % (tuple(gp.shape), tuple(y.shape))
+    g = torch.empty((N, C, H, W), dtype=torch.float32, device=y.device, memory_format=CL)
+    # contraction mode 4: g feeds the stem's weight-gradient GEMM — a sum of up to four window gradients times a scale, so
+    # no input's largest magnitude bounds it: the kernel leaves the exact one
+    slot = _amax.new_slot(y.device) if _mode4() else None
+    _lib.call("dadet_maxpool3x3s2_relu_backward", _p(y), _p(gp), _p(scale), _p(g), N, H, W, C, Ho, Wo,
+              ctypes.c_void_p(slot[0]) if slot else None, _stream())
+    if slot:
+        _amax.attach(g, slot)
+    return g
+
+
 def avgpool_forward(x):
     """[R,C,h,w] channels_last -> [R,C] (mean over h*w)"""
     _dev(x, "x")

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "dadet_colsum_ld": [_P, c_int, _P, c_int64, c_int, c_int, _P, c_size_t, _P],
     "dadet_channel_affine": [_P, _P, _P, _P, c_int64, c_int, c_int, _P],
     "dadet_maxpool3x3s2_forward": [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P],
+    "dadet_maxpool3x3s2_relu_backward": [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P],
     "dadet_avgpool_forward": [_P, _P, c_int, c_int, c_int, _P],
     "dadet_avgpool_backward": [_P, _P, c_int, c_int, c_int, _P],
     "dadet_nchw3_to_nhwc4": [_P, _P, c_int, c_int, c_int, _P],

@@ -18,8 +18,11 @@
 //
 // The 1024->512 1x1 conv (the FLOPs) runs on the MFMA implicit-GEMM kernel with its bias+ReLU epilogue; the
 // kernels here consume its output t[M][C1] one wavefront per row: 64 lanes x float4 along the channel
-// axis, DPP/shuffle wave reduction, one atomic per wavefront for the loss sums.
+// axis, DPP/shuffle wave reduction.  The loss sums are formed in a FIXED order (per wavefront, per workgroup, then over
+// the workgroups' partial sums by da_partials_sum_kernel): the same inputs give the same bits on every run.
 #include "conv_common.h"   // amax_publish (contraction mode 4)
+#include <mutex>
+#include <unordered_map>
 
 namespace dadet {
 
@@ -36,6 +39,7 @@ __device__ inline float bce_with_logits(float x, float y) {
   return (1.f - y) * x + mx + logf(expf(-mx) + expf(-x - mx));
 }
 __device__ inline float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
+constexpr int kDaMaxImg = 8;      // images per launch whose loss sums take the fixed-order path
 
 // grid-stride over rows, one wavefront per row.  sums_out[img][0] += bce, sums_out[img][1] += sigmoid.
 __global__ __launch_bounds__(256) void da_img_fwd_kernel(const float* __restrict__ t,
@@ -43,24 +47,27 @@ __global__ __launch_bounds__(256) void da_img_fwd_kernel(const float* __restrict
                                                          const float* __restrict__ b2,
                                                          const float* __restrict__ labels,
                                                          float* __restrict__ logits_out,
-                                                         float* __restrict__ sums_out, int num_images,
+                                                         float* __restrict__ sums_out,
+                                                         float* __restrict__ partials, int num_images,
                                                          int rows_per_image, int C1) {
-  // per-image sums are collected in LDS first: one global atomic per workgroup, image and quantity (4096 same-address
-  // global atomics — one pair per wavefront — serialised in L2 and made this 33 MB kernel take 112 us)
-  constexpr int kMaxImg = 8;
-  __shared__ float s_acc[kMaxImg * 2];
-  const bool use_lds = num_images <= kMaxImg;
-  if (threadIdx.x < kMaxImg * 2) s_acc[threadIdx.x] = 0.f;
+  // per-image sums: every wavefront owns a row of LDS slots (single writer), the workgroup adds its four rows in a fixed
+  // order and stores partials[block][image][quantity]; da_partials_sum_kernel adds those over the workgroups in a fixed
+  // order.  No float atomics: their order of arrival made the two losses differ in the last bits from run to run.
+  // (more than kDaMaxImg images, no scratch: global atomics as before)
+  constexpr int kMaxImg = kDaMaxImg;
+  __shared__ float s_acc[4][kMaxImg * 2];
+  const bool use_lds = partials != nullptr;
+  if (threadIdx.x < 4 * kMaxImg * 2) (&s_acc[0][0])[threadIdx.x] = 0.f;
   __syncthreads();
-  const int lane = threadIdx.x & 63;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int64_t M = (int64_t)num_images * rows_per_image;
   const float bias = b2[0];
   auto flush = [&](int img, float bce, float sig) {
     if (use_lds) {
-      atomicAdd(&s_acc[img * 2 + 0], bce);
-      atomicAdd(&s_acc[img * 2 + 1], sig);
+      s_acc[wave][img * 2 + 0] += bce;
+      s_acc[wave][img * 2 + 1] += sig;
     } else {
       atomicAdd(&sums_out[img * 2 + 0], bce);
       atomicAdd(&sums_out[img * 2 + 1], sig);
@@ -95,8 +102,26 @@ __global__ __launch_bounds__(256) void da_img_fwd_kernel(const float* __restrict
   }
   if (cur_img >= 0 && lane == 0) flush(cur_img, bce_acc, sig_acc);
   __syncthreads();
-  if (use_lds && threadIdx.x < num_images * 2 && s_acc[threadIdx.x] != 0.f)
-    atomicAdd(&sums_out[threadIdx.x], s_acc[threadIdx.x]);
+  if (use_lds && threadIdx.x < kMaxImg * 2)
+    partials[(size_t)blockIdx.x * (kMaxImg * 2) + threadIdx.x] =
+        ((s_acc[0][threadIdx.x] + s_acc[1][threadIdx.x]) + s_acc[2][threadIdx.x]) + s_acc[3][threadIdx.x];
+}
+
+// out[q] += sum over b < nblocks of partials[b][q] (rows of `stride` floats), one workgroup per quantity q: strided
+// per-thread sums, then a fixed-order tree
+__global__ __launch_bounds__(256) void da_partials_sum_kernel(const float* __restrict__ partials, int nblocks, int stride,
+                                                              float* __restrict__ out) {
+  __shared__ float red[256];
+  const int q = blockIdx.x;
+  float acc = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += 256) acc += partials[(size_t)b * stride + q];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if (threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[q] += red[0];
 }
 
 // backward.  coef[img] = (a_bce_w, a_sig_w, a_bce_x, a_sig_x):
@@ -202,12 +227,11 @@ __global__ __launch_bounds__(256) void da_ins_fwd_kernel(const float* __restrict
                                                          const float* __restrict__ b3,
                                                          const float* __restrict__ labels,
                                                          const float* __restrict__ means, float* __restrict__ logits,
-                                                         float* __restrict__ sums, int R_bce, int R_cst, int n_src,
-                                                         int L, int C) {
-  __shared__ float s_acc[2];
-  if (threadIdx.x < 2) s_acc[threadIdx.x] = 0.f;
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
+                                                         float* __restrict__ sums, float* __restrict__ partials,
+                                                         int R_bce, int R_cst, int n_src, int L, int C) {
+  // (sums in a fixed order, as in da_img_fwd_kernel: partials[block][2], or — no scratch — atomics into sums)
+  __shared__ float s_acc[4][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int R = R_bce + R_cst;
@@ -234,11 +258,15 @@ __global__ __launch_bounds__(256) void da_ins_fwd_kernel(const float* __restrict
     }
   }
   if (lane == 0) {
-    if (bce != 0.f) atomicAdd(&s_acc[0], bce);
-    if (cst != 0.f) atomicAdd(&s_acc[1], cst);
+    s_acc[wave][0] = bce;
+    s_acc[wave][1] = cst;
   }
   __syncthreads();
-  if (threadIdx.x < 2 && s_acc[threadIdx.x] != 0.f) atomicAdd(&sums[threadIdx.x], s_acc[threadIdx.x]);
+  if (threadIdx.x < 2) {
+    const float v = ((s_acc[0][threadIdx.x] + s_acc[1][threadIdx.x]) + s_acc[2][threadIdx.x]) + s_acc[3][threadIdx.x];
+    if (partials) partials[(size_t)blockIdx.x * 2 + threadIdx.x] = v;
+    else if (v != 0.f) atomicAdd(&sums[threadIdx.x], v);
+  }
 }
 
 // coef[0] = d loss / d (BCE sum), coef[1] = d loss / d (consistency sum) (device scalars: upstream gradients x the
@@ -422,6 +450,18 @@ using namespace dadet;
 
 static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// per-workgroup partial loss sums of the two forward kernels: one small buffer per stream, allocated once (work queued on
+// a stream is ordered, so one launch owns it at a time); nullptr when the allocation fails
+constexpr size_t kDaPartialFloats = (size_t)kMaxStreamBlocks * kDaMaxImg * 2;
+static float* da_partials(hipStream_t st) {
+  static std::mutex m;
+  static std::unordered_map<hipStream_t, float*> table;
+  std::lock_guard<std::mutex> lock(m);
+  float*& p = table[st];
+  if (!p && hipMalloc(reinterpret_cast<void**>(&p), sizeof(float) * kDaPartialFloats) != hipSuccess) p = nullptr;
+  return p;
+}
+
 extern "C" int dadet_da_img_head_loss_forward(const float* t, const float* w2, const float* b2,
                                               const float* labels, float* logits_out, float* sums_out,
                                               int num_images, int rows_per_image, int C1, void* stream) {
@@ -434,8 +474,12 @@ extern "C" int dadet_da_img_head_loss_forward(const float* t, const float* w2, c
   int64_t blocks = ceil_div64(M, 4 * 8);  // 4 waves per block, ~8 rows per wave
   if (blocks > kMaxStreamBlocks) blocks = kMaxStreamBlocks;
   if (blocks < 1) blocks = 1;
+  float* partials = num_images <= kDaMaxImg ? da_partials(as_stream(stream)) : nullptr;
   hipLaunchKernelGGL(da_img_fwd_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), t, w2, b2,
-                     labels, logits_out, sums_out, num_images, rows_per_image, C1);
+                     labels, logits_out, sums_out, partials, num_images, rows_per_image, C1);
+  if (partials)
+    hipLaunchKernelGGL(da_partials_sum_kernel, dim3(num_images * 2), dim3(256), 0, as_stream(stream), partials,
+                       (int)blocks, kDaMaxImg * 2, sums_out);
   return check_launch("da_img_head_loss_forward");
 }
 
@@ -527,8 +571,11 @@ extern "C" int dadet_da_ins_tail_forward(const float* h, const float* w3, const 
                 "da_ins_tail_forward: bad pointers");
   int blocks = ceil_div(R_bce + R_cst, 4);
   if (blocks > kNumCU * 2) blocks = kNumCU * 2;
+  float* partials = da_partials(as_stream(stream));
   hipLaunchKernelGGL(da_ins_fwd_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), h, w3, b3, labels, means,
-                     logits, sums, R_bce, R_cst, n_src, levels, C);
+                     logits, sums, partials, R_bce, R_cst, n_src, levels, C);
+  if (partials)
+    hipLaunchKernelGGL(da_partials_sum_kernel, dim3(2), dim3(256), 0, as_stream(stream), partials, blocks, 2, sums);
   return check_launch("da_ins_tail_forward");
 }
 

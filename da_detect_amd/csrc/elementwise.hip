@@ -141,6 +141,71 @@ __global__ void maxpool3x3s2_kernel(const float4* __restrict__ x, float4* __rest
   }
 }
 
+// ---- its backward, fused with the stem's ReLU gate and FrozenBN scale (a trainable stem: FREEZE_CONV_BODY_AT 0) -----
+// reference: F.max_pool2d + F.relu_ + FrozenBatchNorm2d.forward (resnet.py:331-336) differentiated by autograd.
+// Gather form: a thread owns an INPUT pixel (and four channels), visits the at most 2 x 2 windows that cover it, finds each
+// window's argmax again from y and adds gp where the argmax is the pixel itself — no atomics, no index tensor, no zero fill.
+// The argmax of a window is its FIRST maximum in (r, s) scan order (ATen: a later value replaces the running maximum only
+// when strictly greater), per channel: the pixel wins when it is greater than every value scanned before it and not less
+// than any scanned after it.  Contributions are added in ascending (ho, wo) order from 0.f, then the gate, then one
+// multiply by the scale: the fp32 result is ATen's max_pool2d backward * (y > 0) * scale bit for bit.
+__global__ void maxpool3x3s2_relu_backward_kernel(const float4* __restrict__ y, const float4* __restrict__ gp,
+                                                  const float4* __restrict__ scale, float4* __restrict__ g, int N, int H,
+                                                  int W, int C4, int Ho, int Wo, unsigned* __restrict__ amax_out) {
+  const int64_t total = (int64_t)N * H * W * C4;
+  float mo = 0.f;     // contraction mode 4: max|g| (g feeds the stem's weight-gradient GEMM)
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C4);
+    int64_t p = i / C4;
+    const int w = (int)(p % W);
+    p /= W;
+    const int h = (int)(p % H);
+    const int n = (int)(p / H);
+    const float4 yv = y[i];
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    // all four channels gated (all-zero windows behind a ReLU are the common tie): nothing to look at
+    if (yv.x > 0.f || yv.y > 0.f || yv.z > 0.f || yv.w > 0.f) {
+      // window ho covers rows 2 ho - 1 .. 2 ho + 1: an even row lies in one window (as its centre), an odd row in two
+      const int ho0 = h >> 1, ho1 = min((h + 1) >> 1, Ho - 1);
+      const int wo0 = w >> 1, wo1 = min((w + 1) >> 1, Wo - 1);
+      for (int ho = ho0; ho <= ho1; ++ho) {
+        for (int wo = wo0; wo <= wo1; ++wo) {
+          bool fx = true, fy = true, fz = true, fw = true;     // the pixel is the window's first maximum, per channel
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            const int hi = ho * 2 - 1 + r;
+            if (hi < 0 || hi >= H) continue;
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+              const int wi = wo * 2 - 1 + s;
+              if (wi < 0 || wi >= W || (hi == h && wi == w)) continue;
+              const float4 v = y[((int64_t)(n * H + hi) * W + wi) * C4 + c];
+              if (hi < h || (hi == h && wi < w)) {     // scanned before the pixel: it must be strictly greater
+                fx = fx && yv.x > v.x; fy = fy && yv.y > v.y; fz = fz && yv.z > v.z; fw = fw && yv.w > v.w;
+              } else {
+                fx = fx && yv.x >= v.x; fy = fy && yv.y >= v.y; fz = fz && yv.z >= v.z; fw = fw && yv.w >= v.w;
+              }
+            }
+          }
+          const float4 gv = gp[((int64_t)(n * Ho + ho) * Wo + wo) * C4 + c];
+          a.x += fx ? gv.x : 0.f; a.y += fy ? gv.y : 0.f; a.z += fz ? gv.z : 0.f; a.w += fw ? gv.w : 0.f;
+        }
+      }
+    }
+    float4 r;
+    r.x = yv.x > 0.f ? a.x : 0.f; r.y = yv.y > 0.f ? a.y : 0.f;
+    r.z = yv.z > 0.f ? a.z : 0.f; r.w = yv.w > 0.f ? a.w : 0.f;
+    if (scale) {
+      const float4 sc = scale[c];
+      r.x *= sc.x; r.y *= sc.y; r.z *= sc.z; r.w *= sc.w;
+    }
+    g[i] = r;
+    mo = fmaxf(fmaxf(mo, fmaxf(fabsf(r.x), fabsf(r.y))), fmaxf(fabsf(r.z), fabsf(r.w)));
+  }
+  if (amax_out) amax_publish(amax_out, mo);
+}
+
 // ---- global average pool over HW (nn.AvgPool2d(7) on 7x7 maps) --------------------------------
 // sums in raster order like ATen's avg_pool2d CPU kernel (sum then divide by the window size).
 __global__ void avgpool_fwd_kernel(const float4* __restrict__ x, float4* __restrict__ y, int R, int HW,
@@ -532,6 +597,22 @@ extern "C" int dadet_maxpool3x3s2_forward(const float* x, float* y, int N, int H
                      reinterpret_cast<const float4*>(x), reinterpret_cast<float4*>(y), N, H, W, C / 4, Ho,
                      Wo);
   return check_launch("maxpool3x3s2");
+}
+
+extern "C" int dadet_maxpool3x3s2_relu_backward(const float* y, const float* gp, const float* scale, float* g, int N,
+                                                int H, int W, int C, int Ho, int Wo, float* amax_out, void* stream) {
+  DADET_REQUIRE(N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool_relu_backward: bad dims");
+  DADET_REQUIRE(Ho == (H + 2 - 3) / 2 + 1 && Wo == (W + 2 - 3) / 2 + 1, "maxpool_relu_backward: Ho/Wo mismatch");
+  if (N == 0) return DADET_OK;
+  DADET_REQUIRE(y && gp && g && aligned16(y) && aligned16(gp) && aligned16(scale) && aligned16(g),
+                "maxpool_relu_backward: bad pointers");
+  DADET_REQUIRE((int64_t)N * H * W < (1LL << 31), "maxpool_relu_backward: tensor too large for 32-bit pixel indexing");
+  const int64_t total = (int64_t)N * H * W * (C / 4);
+  hipLaunchKernelGGL(maxpool3x3s2_relu_backward_kernel, dim3(stream_blocks(total, 256)), dim3(256), 0, as_stream(stream),
+                     reinterpret_cast<const float4*>(y), reinterpret_cast<const float4*>(gp),
+                     reinterpret_cast<const float4*>(scale), reinterpret_cast<float4*>(g), N, H, W, C / 4, Ho, Wo,
+                     reinterpret_cast<unsigned*>(amax_out));
+  return check_launch("maxpool3x3s2_relu_backward");
 }
 
 extern "C" int dadet_avgpool_forward(const float* x, float* y, int R, int HW, int C, void* stream) {

@@ -454,6 +454,36 @@ class BottleneckWithFixedBatchNorm(Bottleneck):
             norm_func=FrozenBatchNorm2d, dcn_config=dcn_config)
 
 
+class _StemFn(torch.autograd.Function):
+    """The stem with a trainable weight (MODEL.BACKBONE.FREEZE_CONV_BODY_AT 0) as ONE autograd node.
+
+    forward : the frozen stem's two launches — the 7x8x4 implicit GEMM with the FrozenBN affine and the ReLU in its
+              epilogue, then the max pool.
+    backward: g = [y > 0] * scale * (gp routed to each pooling window's first maximum, ATen's tie rule)   1 launch
+              dW4 = wgrad(x4, g) on the padded [64,4,7,8] shape                                           1 GEMM (+ reduce)
+    w4 is the zero-padded copy that F.pad makes of the parameter: autograd slices dW4 back to [64,3,7,7] (the fourth input
+    channel and the eighth kernel column are padding; what lands there is dropped).  w4 is no leaf, so the gradient never
+    takes the direct-accumulation path into the parameter's gradient buffer, whose shape it does not have.  The image
+    takes no gradient, nor do the FrozenBN buffers."""
+
+    @staticmethod
+    def forward(ctx, x4, w4, scale, shift, out_size):
+        y = _C.conv_forward(x4, w4, scale, shift, stride=2, pad=3, relu_mode=1, out_size=out_size)
+        ctx.w_shape = tuple(w4.shape)
+        ctx.save_for_backward(x4, y, scale)
+        return _C.maxpool3x3s2(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gp):
+        x4, y, scale = ctx.saved_tensors
+        g = _C.maxpool3x3s2_relu_backward(y, gp, scale)
+        lane = WgradLane(gp.device)
+        dw4 = lane.run(lambda: _C.conv_wgrad(x4, g, ctx.w_shape, 2, 3), x4, g)
+        lane.join()
+        return None, dw4, None, None, None
+
+
 class BaseStem(nn.Module):
     """conv 7x7/2 (3 -> 64) + FrozenBN + ReLU + maxpool 3x3/2 (resnet.py:317-336)"""
 
@@ -470,7 +500,8 @@ class BaseStem(nn.Module):
         w = self.conv1.weight
         if w.requires_grad and torch.is_grad_enabled():
             return F.pad(w, (0, 1, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last)
-        key = (w._version, w.device)
+        # (the weight epoch: the fused optimizer updates a trainable stem through raw pointers, without a version bump)
+        key = (w._version, w.device, _C.weight_epoch() if w.requires_grad else 0)
         if self._w4 is None or self._w4[0] != key:
             with torch.no_grad():
                 self._w4 = (key, F.pad(w, (0, 1, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last))
@@ -482,10 +513,10 @@ class BaseStem(nn.Module):
         x4 = _C.nchw3_to_nhwc4(x)
         out_size = _C.conv_out_size(H, W, 7, 7, 2, 3)
         scale, shift = self.bn1.folded()
-        y = conv2d_affine_act(x4, self._padded_weight(), scale, shift, None, 2, 3, True, out_size)
-        if y.requires_grad:
-            raise NotImplementedError("max-pool backward: the stem is frozen in every DA configuration "
-                                      "(MODEL.BACKBONE.FREEZE_CONV_BODY_AT >= 1)")
+        w4 = self._padded_weight()
+        if N > 0 and torch.is_grad_enabled() and w4.requires_grad:     # the stem activation requires grad
+            return _StemFn.apply(x4, w4, scale, shift, out_size)
+        y = conv2d_affine_act(x4, w4, scale, shift, None, 2, 3, True, out_size)
         return _C.maxpool3x3s2(y)
 
 

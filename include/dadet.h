@@ -567,9 +567,17 @@ int dadet_colsum(const float* g, float* out, int64_t rows, int C, void* workspac
 /* y = x * scale[c] + bias[c]  (standalone FrozenBatchNorm2d, layers/batch_norm.py:19-24) */
 int dadet_channel_affine(const float* x, const float* scale, const float* bias, float* y, int64_t rows,
                          int C, int relu, void* stream);
-/* 3x3 stride-2 pad-1 max pool, NHWC (BaseStem, resnet.py:335); forward only (stem is frozen). */
+/* 3x3 stride-2 pad-1 max pool, NHWC (BaseStem, resnet.py:335) */
 int dadet_maxpool3x3s2_forward(const float* x, float* y, int N, int H, int W, int C, int Ho, int Wo,
                                void* stream);
+/* ... its backward fused with the stem's ReLU gate and FrozenBN scale (a trainable stem, FREEZE_CONV_BODY_AT 0):
+ * y [N,H,W,C] the activation in front of the pool (conv + FrozenBN + ReLU, so y >= 0), gp [N,Ho,Wo,C] the gradient of the
+ * pooled map, scale [C] or NULL (= 1); g [N,H,W,C] = (y > 0 ? sum of gp over the windows whose argmax is the pixel : 0)
+ * * scale[c], the gradient of the convolution output.  The argmax of a window is its first maximum in (r, s) scan order
+ * and a pixel's windows are summed in ascending (ho, wo) order: ATen's max_pool2d backward bit for bit, deterministic.
+ * amax_out: NULL, or a zeroed slot that receives max|g| (contraction mode 4, see dadet_conv_forward_scaled). */
+int dadet_maxpool3x3s2_relu_backward(const float* y, const float* gp, const float* scale, float* g, int N, int H,
+                                     int W, int C, int Ho, int Wo, float* amax_out, void* stream);
 /* global average pool over HW (nn.AvgPool2d(7) on 7x7 maps: roi_box_predictors.py:17,29; da_heads.py:89,403) */
 int dadet_avgpool_forward(const float* x, float* y, int R, int HW, int C, void* stream);
 int dadet_avgpool_backward(const float* gy, float* gx, int R, int HW, int C, void* stream);

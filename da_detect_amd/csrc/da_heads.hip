@@ -18,8 +18,9 @@
 //
 // The 1024->512 1x1 conv (the FLOPs) runs on the MFMA implicit-GEMM kernel with its bias+ReLU epilogue; the
 // kernels here consume its output t[M][C1] one wavefront per row: 64 lanes x float4 along the channel
-// axis, DPP/shuffle wave reduction.  The loss sums are formed in a FIXED order (per wavefront, per workgroup, then over
-// the workgroups' partial sums by da_partials_sum_kernel): the same inputs give the same bits on every run.
+// axis, DPP/shuffle wave reduction.  The loss sums — image head, instance tail and the triplet hinge sum — are formed in a
+// FIXED order (per wavefront, per workgroup, then over the workgroups' partial sums by da_partials_sum_kernel): the same
+// inputs give the same bits on every run.
 #include "conv_common.h"   // amax_publish (contraction mode 4)
 #include <mutex>
 #include <unordered_map>
@@ -386,13 +387,17 @@ __global__ __launch_bounds__(256) void da_ins_merge_kernel(const float4* __restr
 // a, p, n: [H][W][C] (one image each).  For every (h, c): d_ap = ||a - p + eps||_2 over w, d_an likewise;
 // loss_sum += max(d_ap - d_an + margin, 0).  A lane owns one (h, c) pair — lanes run along c, so every
 // w step is a coalesced row read and no cross-lane reduction is needed until the final sum.
-// dist_out[(h*C + c)*2 + {0,1}] keeps (d_ap, d_an) for the backward.
+// dist_out[(h*C + c)*2 + {0,1}] keeps (d_ap, d_an) for the backward.  The hinge sum is formed in a fixed order, as in
+// da_img_fwd_kernel: wave sum, the workgroup's four LDS slots, partials[block], then da_partials_sum_kernel (no scratch:
+// one atomic per wavefront into loss_sum).
 __global__ __launch_bounds__(256) void triplet_w_fwd_kernel(const float* __restrict__ a,
                                                             const float* __restrict__ p,
                                                             const float* __restrict__ n, int H, int W, int C,
                                                             float margin, float eps,
                                                             float* __restrict__ dist_out,
-                                                            float* __restrict__ loss_sum) {
+                                                            float* __restrict__ loss_sum,
+                                                            float* __restrict__ partials) {
+  __shared__ float s_acc[4];
   const int64_t total = (int64_t)H * C;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -413,7 +418,14 @@ __global__ __launch_bounds__(256) void triplet_w_fwd_kernel(const float* __restr
     acc += fmaxf(dap - dan + margin, 0.f);
   }
   acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) atomicAdd(loss_sum, acc);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (!partials) {
+    if (lane == 0) atomicAdd(loss_sum, acc);
+    return;
+  }
+  if (lane == 0) s_acc[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((s_acc[0] + s_acc[1]) + s_acc[2]) + s_acc[3];
 }
 
 // g_scale[0] = upstream gradient / (H*C)  (mean reduction).  d/da = g*( (a-p+eps)/d_ap - (a-n+eps)/d_an ),
@@ -450,7 +462,7 @@ using namespace dadet;
 
 static bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// per-workgroup partial loss sums of the two forward kernels: one small buffer per stream, allocated once (work queued on
+// per-workgroup partial loss sums of the three forward kernels: one small buffer per stream, allocated once (work queued on
 // a stream is ordered, so one launch owns it at a time); nullptr when the allocation fails
 constexpr size_t kDaPartialFloats = (size_t)kMaxStreamBlocks * kDaMaxImg * 2;
 static float* da_partials(hipStream_t st) {
@@ -542,8 +554,12 @@ extern "C" int dadet_triplet_w_forward(const float* anchor, const float* positiv
   DADET_REQUIRE(anchor && positive && negative && dist_out && loss_sum, "triplet_w_forward: null pointer");
   int64_t blocks = ceil_div64((int64_t)H * C, 256);
   if (blocks > kMaxStreamBlocks) blocks = kMaxStreamBlocks;
+  float* partials = da_partials(as_stream(stream));
   hipLaunchKernelGGL(triplet_w_fwd_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), anchor,
-                     positive, negative, H, W, C, margin, eps, dist_out, loss_sum);
+                     positive, negative, H, W, C, margin, eps, dist_out, loss_sum, partials);
+  if (partials)
+    hipLaunchKernelGGL(da_partials_sum_kernel, dim3(1), dim3(256), 0, as_stream(stream), partials, (int)blocks, 1,
+                       loss_sum);
   return check_launch("triplet_w_forward");
 }
 

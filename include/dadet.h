@@ -605,7 +605,9 @@ int dadet_rpn_decode_clip(const float* deltas, const float* anchors, const int64
  *   logit[m]          = sum_c t[m][c] * w2[c] + b2[0]                    (conv2_da, 1x1 -> 1 channel)
  *   sums[img][0]     += BCE-with-logits(logit[m], labels[img])           (da_heads/loss.py:95-97)
  *   sums[img][1]     += sigmoid(logit[m])                                (consistency_loss.py:12-14)
- * one wavefront per row, wave-reduced, one atomic per wavefront; the caller zeroes `sums` [num_images][2].
+ * one wavefront per row, wave-reduced; the sums are added in a fixed order (per wavefront, per workgroup, then over the
+ * workgroups' partials in a per-stream scratch), so equal inputs give equal bits; more than 8 images, or no scratch: one
+ * atomic per wavefront and image.  The caller zeroes `sums` [num_images][2].
  * ----------------------------------------------------------------------------------------------*/
 int dadet_da_img_head_loss_forward(const float* t, const float* w2, const float* b2, const float* labels,
                                    float* logits_out, float* sums_out, int num_images,
@@ -636,7 +638,8 @@ int dadet_da_img_head_loss_backward_gm(const float* t, const float* w2, const fl
                                        int rows_per_image, int C1, float* amax_w, float* amax_x, void* stream);
 /* Domain-level triplet loss on NHWC maps [H][W][C] (one image each): L2 distance over the W axis with
  * eps, hinge with margin, loss_sum[0] += sum over (h,c) (the caller zeroes it and divides by H*C).
- * dist_out [H*C][2] keeps (d_ap, d_an) for the backward; g_scale[0] = upstream grad / (H*C).
+ * dist_out [H*C][2] keeps (d_ap, d_an) for the backward; g_scale[0] = upstream grad / (H*C).  loss_sum is added in the
+ * same fixed order as the image head's sums.
  * reference: da_heads/loss.py:180-200 (nn.TripletMarginLoss(margin, p=2) on [1,C,H,W]). */
 /* Instance-level domain classifier tail — replaces, per iteration, the last layer of `DAInsHead.forward`
  * (modeling/da_heads/da_heads.py:61-68), `F.binary_cross_entropy_with_logits` of the instance logits

@@ -364,23 +364,7 @@ def conv_forward(x, w, scale=None, bias=None, addend=None, mask_ref=None, stride
         key = (N * Ho * Wo, Cout, Cin * KH * KW, KH, pad, out_spatial_stride)
         kname = _KNAME_CACHE.get(key)
         if kname is None:
-            variant = _lib.load().dadet_conv_forward_variant(ctypes.byref(d))
-            mode = get_gemm_mode()
-            if variant == 4:
-                kname = "conv_big_kernel<256>"
-            elif variant == 5:
-                kname = "conv_big128_kernel"
-            elif variant == 3:
-                # panel width as csrc/conv_ws.hip's launch_fwd_ws picks it: K = 256 runs 128-column panels on layers of
-                # at least 256 columns (mode 4, unless DADET_WS_K256_BN=64), 64-column panels otherwise
-                bn = 128
-                if Cin == 256:
-                    wide = mode == 4 and Cout >= 256 and os.environ.get("DADET_WS_K256_BN", "") != "64"
-                    bn = 128 if wide else 64
-                kname = "conv1x1_ws_kernel<%d,%d,%d>" % (Cin, bn, mode)
-            else:
-                kname = ("conv_fwd_kernel<%s>" if mode == 0 else ("conv_fwd_split_kernel<%%s,%d>" % mode)) % \
-                    ("2,2", "2,1", "1,1")[variant]
+            kname = _plan_name("dadet_conv_forward_plan", d)
             _KNAME_CACHE[key] = kname
         if getattr(PROFILER, "detail", False):   # tools/gemm_table.py: one row per problem shape
             # rows issued on a side stream share the GPU with the compute stream's kernels: their rates are not the kernel's
@@ -573,14 +557,15 @@ class WgradBatch(list):
     (conv_wgrad(..., pending=batch) ... conv_wgrad_reduce_batch(batch)); keeps their workspaces alive until then"""
 
 
-def _wgrad_kname(d, dense_rows):
-    """the kernel a weight-gradient launch of this shape runs (profiling labels)"""
-    mode = get_gemm_mode()
-    if mode == 0:
-        return "conv_wgrad_kernel"
-    if dense_rows and _lib.load().dadet_conv_wgrad_variant(ctypes.byref(d)) == 1:
-        return "conv_wgrad_big_kernel"
-    return "conv_wgrad_split_kernel<%d>" % mode
+def _plan_name(query, d, *args):
+    """the kernel a launch of this descriptor runs, as the library's plan names it (profiling labels)"""
+    info = _lib.ConvPlanInfo()
+    _lib.call(query, ctypes.byref(d), *(args + (ctypes.byref(info),)))
+    return info.name.decode()
+
+
+def _wgrad_kname(d, gy_ld):
+    return _plan_name("dadet_conv_wgrad_plan", d, int(gy_ld))
 
 
 def conv_wgrad_reduce_batch(batch):
@@ -697,7 +682,7 @@ def conv_wgrad(x, gy, weight_shape, stride=1, pad=0, out_scale=None, dw=None, ac
                       1 if accumulate else 0, _p(ws), ctypes.c_size_t(ws.numel()), ctypes.byref(item), _stream())
 
         if PROFILER is not None:
-            kname = _wgrad_kname(d, gy_ld == Cout)
+            kname = _wgrad_kname(d, gy_ld)
             if getattr(PROFILER, "detail", False):
                 kname = "%s|M=%d N=%d K=%d k%dx%d s%d" % (kname, N * Ho * Wo, Cout, Cin * KH * KW, KH, KW, stride)
             with PROFILER.span(kname, 2.0 * N * Ho * Wo * Cout * Cin * KH * KW,
@@ -710,7 +695,7 @@ def conv_wgrad(x, gy, weight_shape, stride=1, pad=0, out_scale=None, dw=None, ac
         return dw
     ws = _workspace(nbytes.value, x.device)
     if PROFILER is not None:
-        kname = _wgrad_kname(d, gy_ld == Cout)
+        kname = _wgrad_kname(d, gy_ld)
         if getattr(PROFILER, "detail", False):
             kname = "%s|M=%d N=%d K=%d k%dx%d s%d" % (kname, N * Ho * Wo, Cout, Cin * KH * KW, KH, KW, stride)
         with PROFILER.span(kname,

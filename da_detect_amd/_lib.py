@@ -23,6 +23,15 @@ class ConvDesc(ctypes.Structure):
         "out_spatial_stride", "relu_mode")]
 
 
+class ConvPlanInfo(ctypes.Structure):
+    """mirror of dadet_conv_plan_info (include/dadet.h)"""
+
+    _fields_ = [(n, c_int) for n in (
+        "family", "variant", "tiles_m", "tiles_n", "ksplit", "splits", "rows_per_split", "sk_dp_tiles", "sk_tiles", "sk_units",
+        "sk_iters", "sk_max_parts", "big_splits", "big_body", "launches", "grid", "needs_counters")] + [
+        ("workspace_bytes", c_size_t), ("name", ctypes.c_char * 64)]
+
+
 class WgradPending(ctypes.Structure):
     """mirror of dadet_wgrad_pending (include/dadet.h)"""
 
@@ -90,6 +99,8 @@ _SIGNATURES = {
     "dadet_amax": [_P, ctypes.c_longlong, _P, _P],
     "dadet_amax_batch": [_P, c_int, c_int, _P],
     "dadet_conv_forward_variant": [POINTER(ConvDesc)],
+    "dadet_conv_forward_plan": [POINTER(ConvDesc), POINTER(ConvPlanInfo)],
+    "dadet_conv_wgrad_plan": [POINTER(ConvDesc), c_int, POINTER(ConvPlanInfo)],
     "dadet_set_gemm_mode": [c_int],
     "dadet_get_gemm_mode": [],
     "dadet_conv_wgrad_variant": [POINTER(ConvDesc)],

@@ -1162,100 +1162,11 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_big_group_kernel(const Wgra
   wgrad_big_body(g.a[i], local);
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------------
-// 0: never, 1: where the plan below expects a gain, 2: wherever the kernel is applicable (tests).  DADET_BIG_GEMM sets the
-// start-up value (A/B runs); dadet_set_big_gemm changes it at run time
-static int g_big_mode = [] {
-  const char* e = getenv("DADET_BIG_GEMM");
-  const int v = e ? atoi(e) : 1;
-  return v >= 0 && v <= 2 ? v : 1;
-}();
-
-// Number of K ranges a tile's reduction is cut into.  Reductions of K >= 8192 (the RPN 3x3 conv) are ALWAYS cut in two: the
-// hand-over (the last part reads one parked tile, ~4 us) is small against 288 K-tiles per tile, and the result of that
-// layer then does not depend on how many rows the launch happens to have — the overlapped training schedule runs the RPN
-// head on the labelled images only, the plain one on all of them, and tests/test_full_size_gpu.py asks both for the same
-// sampled ROIs.  Shorter reductions are cut in two only when the grid leaves half of the CUs without a tile.  (The bound
-// was K >= 4096 until the box head of the recipes that pool BOTH images showed what that costs: res5 3x3 on 512 ROIs is 196
-// tiles — two parts are 392 workgroups, two rounds on 256 CUs, where one part per tile is one round: `da` 17.77 -> 17.53,
-// `triplet` 21.81 -> 21.60 ms per step.  The box head sees the same rows in every schedule.)
-static int big_split_plan(const int tiles, const int nk) {
-  if (const char* e = getenv("DADET_BIG_SPLITS")) {     // read per call: tests and A/B runs force the part count
-    const int v = atoi(e);
-    if (v >= 1 && v <= 8 && nk / v >= 1) return v;
-  }
-  if (nk >= 256) return 2;
-  return (tiles <= kNumCU / 2 && nk >= 16) ? 2 : 1;
-}
-
-// which large-tile kernel serves this problem: 0 none, 1 the 256 x 256 tile, 2 the 256 x 128 tile
-int big_variant(const ConvArgs& a) {
-  if (g_big_mode == 0) return 0;
-  if (a.os != 1 || !a.epi_v4 || a.Cin % 32 != 0 || a.K % 32 != 0 || a.Cout % 4 != 0) return 0;
-  if (a.x_bytes >= 0x7FFFFF00u || a.w_bytes >= 0x7FFFFF00u || a.y_bytes >= 0x7FFFFF00u) return 0;
-  if (a.M >= (1 << 24)) return 0;
-  if (g_big_mode == 2) {                       // tests: wherever applicable; DADET_BIG_TILE_N picks the tile width
-    const char* e = getenv("DADET_BIG_TILE_N");
-    return (e && atoi(e) == 128) ? 2 : 1;
-  }
-  // plan (tools/native/gemm_lab.hip, profiles/r05_gemm_lab.txt): +29 .. +35% against the 128 x 128 kernel where the grid fills
-  // the chip with at most two K parts per tile; 64 tiles of 256 x 256 in four parts — res4 3x3 — only equal it (the last
-  // part reads 768 KB), so layers of up to 256 output channels take the 256 x 128 tile
-  if (a.K < 512 || a.M < 4096 || a.Cout < 128) return 0;
-  const int tm = ceil_div(a.M, 256);
-  // 129 .. 256 output channels over at least 96 row tiles (the pyramid's 256-channel 3x3 / lateral layers on P2 / P3,
-  // M = 262144 / 65536): one column of 256 x 256 tiles fills the chip without any K split, on the kernel whose loop holds
-  // the matrix pipe 84% of the time instead of 61% (round 6; DADET_BIG_N256_WIDE=0: the 256 x 128 tile as before)
-  static const bool wide256 = !(getenv("DADET_BIG_N256_WIDE") && getenv("DADET_BIG_N256_WIDE")[0] == '0');
-  if (wide256 && a.Cout > 128 && a.Cout <= 256 && tm >= 96) return 1;
-  if (a.Cout <= 256) return tm * ceil_div(a.Cout, 128) >= 96 ? 2 : 0;
-  return tm * ceil_div(a.Cout, 256) >= 96 ? 1 : 0;
-}
-bool big_eligible(const ConvArgs& a) { return big_variant(a) != 0; }
-
-static int big_tiles(const ConvArgs& a, const int variant) {
-  return ceil_div(a.M, 256) * ceil_div(a.Cout, variant == 2 ? 128 : 256);
-}
-
-// Tail cut: a grid of a few tiles more than a multiple of the CU count (the res5 head on 512 ROIs: 98 x 8 = 784 tiles of
-// 256 x 256, 3.06 rounds) runs its last, nearly empty round for a whole tile's time — a fifth of `M=25088 N=2048 K=512`'s
-// 265 us.  The tiles of that round (at most a quarter of the chip) are cut into two parts instead (the symmetric meeting):
-// twice the workgroups, half the round.  -> number of whole-tile workgroups (0: no tail cut).  DADET_BIG_TAIL=0: never.
-static int big_tail_plan(const int tiles, const int nk) {
-  const char* e = getenv("DADET_BIG_TAIL");
-  if (e && e[0] == '0') return 0;
-  if (getenv("DADET_BIG_SPLITS")) return 0;       // a forced uniform cut (tests, A/B runs)
-  const int tail = tiles % kNumCU;
-  if (tiles <= kNumCU || tiles > 2048 || tail == 0 || tail > kNumCU / 4 || nk < 4) return 0;
-  return tiles - tail;
-}
-
-size_t big_workspace_bytes(const ConvArgs& a) {
-  const int variant = big_variant(a);
-  if (!variant) return 0;
-  const int tiles = big_tiles(a, variant);
-  const size_t tile_bytes = (size_t)256 * (variant == 2 ? 128 : 256) * sizeof(float);
-  const int s = tiles <= 2048 ? big_split_plan(tiles, a.K / 32) : 1;
-  if (s > 1) return (size_t)tiles * s * tile_bytes;
-  const int body = big_tail_plan(tiles, a.K / 32);
-  return body ? (size_t)(tiles - body) * 2 * tile_bytes : 0;
-}
-
-int launch_fwd_big(ConvArgs& a, hipStream_t st, float* ws, int* counters) {
-  const int variant = big_variant(a);
-  const int bn = variant == 2 ? 128 : 256;
-  a.tiles_m = ceil_div(a.M, 256);
-  a.tiles_n = ceil_div(a.Cout, bn);
-  const int tiles = a.tiles_m * a.tiles_n;
-  a.big_splits = (ws && counters && tiles <= 2048) ? big_split_plan(tiles, a.K / 32) : 1;
-  a.big_body = 0;
-  if (a.big_splits == 1 && ws && counters) {
-    a.big_body = big_tail_plan(tiles, a.K / 32);
-    if (a.big_body) a.big_splits = 2;
-  }
-  const int grid = a.big_body ? a.big_body + (tiles - a.big_body) * a.big_splits : tiles * a.big_splits;
-  a.sk_ws = ws;
-  a.sk_counters = counters;
+// ---- host side: launch what the plan says (conv_plan.h) ---------------------------------------------------------------
+// a.tiles_m / tiles_n / big_splits / big_body come from the plan; a.sk_ws / sk_counters: the stream's scratch of
+// p.workspace_bytes and its zeroed counters (null when the plan needs none)
+int launch_fwd_big(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st) {
+  const int variant = p.family == plan::kFwdBig128 ? 2 : 1;
   {
     const char* e = getenv("DADET_BIG_ASYM");       // read per call: A/B runs and tests
     a.big_asym = (e && e[0] == '1') ? 1 : 0;
@@ -1275,47 +1186,12 @@ int launch_fwd_big(ConvArgs& a, hipStream_t st, float* ws, int* counters) {
     }
     attr_set[variant] = true;
   }
-  if (variant == 2) hipLaunchKernelGGL(conv_big128_kernel, dim3(grid), dim3(512), lds, st, a);
-  else hipLaunchKernelGGL((conv_big_kernel<256>), dim3(grid), dim3(512), lds, st, a);
+  if (variant == 2) hipLaunchKernelGGL(conv_big128_kernel, dim3(p.grid), dim3(512), lds, st, a);
+  else hipLaunchKernelGGL((conv_big_kernel<256>), dim3(p.grid), dim3(512), lds, st, a);
   return check_launch("conv_forward(big)");
 }
 
-// ---- weight gradient: plan and launch -----------------------------------------------------------------------------
-// The grid is small (Cout x K in tiles of 256 x 256: 4 .. 72 tiles), so the reduction over the M rows is cut into `splits`
-// ranges of whole K-tiles that fill the 256 CUs once.  Returns false when the 128 x 128 kernel should run.
-bool wgrad_big_plan(const dadet_conv_desc* d, int* tiles_co, int* tiles_kc, int* splits, int* rps) {
-  static const bool enabled = !(getenv("DADET_WGRAD_BIG") && getenv("DADET_WGRAD_BIG")[0] == '0');   // A/B runs
-  if (!enabled || g_big_mode == 0 || gemm_mode() != 4) return false;
-  const int M = d->N * d->Ho * d->Wo, K = d->KH * d->KW * d->Cin;
-  if (d->Cin % 4 != 0 || K % 4 != 0 || M >= (1 << 24)) return false;
-  if ((uint64_t)d->N * d->H * d->W * d->Cin * 4 >= 0x7FFFFF00ull || (uint64_t)M * ((d->Cout + 3) / 4 * 4) * 4 >= 0x7FFFFF00ull)
-    return false;
-  if (g_big_mode != 2 && (d->Cout < 256 || K < 256 || M < 2048)) return false;
-  *tiles_co = ceil_div(d->Cout, 256);
-  *tiles_kc = ceil_div(K, 256);
-  const int tiles = (*tiles_co) * (*tiles_kc);
-  // Every workgroup leaves a 256 KB tile of partial sums: 64 MB per launch once the chip is full, whatever the layer.  A
-  // weight of four tiles (res4's 1x1 layers: 1 MB) would be cut into 64 parts — 64 MB written and read again for 41 us of
-  // GEMM, where the 128 x 128 kernel's 16 tiles need a quarter of that traffic for 47 us: below eight tiles it keeps the
-  // layer (profiles/r05_step_timeline_img_only.txt: the step-end reduction passes read what these launches park)
-  static const int min_tiles = getenv("DADET_WGRAD_BIG_MIN_TILES") ? atoi(getenv("DADET_WGRAD_BIG_MIN_TILES")) : 8;
-  if (g_big_mode != 2 && tiles < min_tiles) return false;
-  int s = kNumCU / tiles;
-  if (const char* e = getenv("DADET_WGRAD_BIG_SPLITS")) { const int v = atoi(e); if (v > 0) s = v; }
-  if (s < 1) s = 1;
-  // a part is ONE fp32 accumulator chain over its rows: beyond ~4096 rows the chain's own rounding shows against the
-  // exact-fp32 kernel, whose plan always cuts (tests/test_ops_gpu.py::test_split_bf16_accuracy_at_production_k: the RPN
-  // conv's dense gradient, 8192 rows x 144 tiles in one part, RMS 1.27e-6 against 1.01e-6) — at least ceil(M / 4096) parts
-  // (the step has no such launch: its 144-tile weight is the RPN conv, whose gradient runs on the <= 256 sampled rows)
-  if (!getenv("DADET_WGRAD_BIG_SPLITS") && s < ceil_div(M, 4096)) s = ceil_div(M, 4096);
-  const int max_s = ceil_div(M, 128);                 // at least four K-tiles per part
-  if (s > max_s) s = max_s;
-  const int rows = ceil_div(ceil_div(M, s), 32) * 32;
-  *rps = rows;
-  *splits = ceil_div(M, rows);
-  return true;
-}
-
+// ---- weight gradient (the plan: conv_plan.h, wgrad_big_plan / plan_wgrad_group) ----------------------------------------
 constexpr size_t kWgradBigLds = 2 * 4 * 256 * 64 + 2 * 256 * sizeof(int4);      // two K-tile slots + group 1's row state
 
 int launch_wgrad_big(WgradArgs& a, hipStream_t st) {
@@ -1331,54 +1207,6 @@ int launch_wgrad_big(WgradArgs& a, hipStream_t st) {
   }
   hipLaunchKernelGGL(conv_wgrad_big_kernel, dim3(a.tiles_co * a.tiles_kc * a.splits), dim3(512), kWgradBigLds, st, a);
   return check_launch("conv_wgrad(big)");
-}
-
-// can this weight gradient be a member of a grouped launch (the tile kernel's own conditions; no lower bound on the tiles)
-bool wgrad_group_member(const dadet_conv_desc* d) {
-  static const bool enabled = !(getenv("DADET_WGRAD_BIG") && getenv("DADET_WGRAD_BIG")[0] == '0');
-  if (!enabled || g_big_mode == 0 || gemm_mode() != 4) return false;
-  const int M = d->N * d->Ho * d->Wo, K = d->KH * d->KW * d->Cin;
-  if (d->Cin % 4 != 0 || K % 4 != 0 || d->Cout % 4 != 0 || M >= (1 << 24) || M < 256) return false;
-  if ((uint64_t)d->N * d->H * d->W * d->Cin * 4 >= 0x7FFFFF00ull || (uint64_t)M * d->Cout * 4 >= 0x7FFFFF00ull) return false;
-  return g_big_mode == 2 || (d->Cout >= 256 && K >= 256 && M >= 2048);
-}
-
-// Rows per part R (a multiple of 32, the same for every problem of the group — every workgroup then runs the same number
-// of K-tiles on one tile, whatever its problem): the smallest R whose parts fit the chip's workgroup slots (256 for the
-// 256 x 256 tile, 2 x 256 for the 128 x 128 kernel), at least 128 rows (four K-tiles), at most 4096 (+ an eighth where that saves a round of workgroups).
-// splits[i] = ceil(M_i / R).
-// DADET_WGRAD_GROUP_ROWS forces R (tests).
-void wgrad_group_plan(const int n, const dadet_conv_desc* d, const int tile, int* tiles_co, int* tiles_kc, int* splits,
-                      int* rows) {
-  const int slots = tile == 256 ? kNumCU : 2 * kNumCU;
-  int max_m = 0;
-  for (int i = 0; i < n; ++i) {
-    tiles_co[i] = ceil_div(d[i].Cout, tile);
-    tiles_kc[i] = ceil_div(d[i].KH * d[i].KW * d[i].Cin, tile);
-    const int M = d[i].N * d[i].Ho * d[i].Wo;
-    max_m = M > max_m ? M : max_m;
-  }
-  int R = 128;
-  if (const char* e = getenv("DADET_WGRAD_GROUP_ROWS")) {
-    const int v = atoi(e);
-    R = v >= 32 ? v / 32 * 32 : R;
-  } else {
-    const int top = ceil_div(max_m, 32) * 32;
-    for (; R < top; R += 32) {
-      int wgs = 0;
-      for (int i = 0; i < n; ++i) wgs += tiles_co[i] * tiles_kc[i] * ceil_div(d[i].N * d[i].Ho * d[i].Wo, R);
-      if (wgs <= slots) break;
-    }
-    // one part is ONE fp32 accumulator chain over its rows: never more than 4096 of them (wgrad_big_plan's bound, for the
-    // same reason) — a group whose tiles alone nearly fill the slots (the res5 head on 512 ROIs: ~100 tiles x 25088 rows)
-    // then takes a second / third round of workgroups, cut into equal parts rather than 4096 + a remainder
-    // (an eighth of slack: the res5 head on 256 ROIs — 68 tiles, 12544 rows — fits the slots in three parts of 4192 rows;
-    // cutting it into four of 3136 is 272 workgroups, a second round for 16 of them: the family went 1.8 -> 2.2 ms per step)
-    const int cap = ceil_div(ceil_div(max_m, ceil_div(max_m, 4096)), 32) * 32;
-    if (R > 4096 + 512) R = cap;
-  }
-  *rows = R;
-  for (int i = 0; i < n; ++i) splits[i] = ceil_div(d[i].N * d[i].Ho * d[i].Wo, R);
 }
 
 int launch_wgrad_big_group(const WgradArgs* a, const int n, hipStream_t st) {
@@ -1407,13 +1235,3 @@ int launch_wgrad_big_group(const WgradArgs* a, const int n, hipStream_t st) {
 }
 
 }  // namespace dadet
-
-extern "C" int dadet_set_big_gemm(int mode) {
-  if (mode < 0 || mode > 2) {
-    dadet::set_error("set_big_gemm: mode must be 0 (off), 1 (planned) or 2 (wherever applicable)");
-    return DADET_EINVAL;
-  }
-  dadet::g_big_mode = mode;
-  return DADET_OK;
-}
-extern "C" int dadet_get_big_gemm(void) { return dadet::g_big_mode; }

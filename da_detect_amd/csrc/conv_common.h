@@ -1,8 +1,14 @@
-// Shared declarations of the implicit-GEMM convolution kernels (conv_igemm.hip: exact fp32 MFMA;
-// conv_split.hip: split-bf16 MFMA).
+// Shared declarations of the implicit-GEMM convolution kernels: device helpers (buffer access, operand splits, maxima, the
+// non-finite guard), the kernel argument structs, and the launchers that conv_dispatch.hip calls with a plan (conv_plan.h).
+//   conv_igemm.hip  exact fp32 MFMA (contraction mode 0)
+//   conv_split.hip  128 / 64-wide tiles on split operands: three / two bf16 terms (modes 3 / 2), two fp16 terms (mode 4)
+//   conv_ws.hip     weight-stationary 1x1 kernel (modes 3, 4)
+//   conv_big.hip    256 x 256 / 256 x 128 tiles (mode 4)
+//   conv_aux.hip    reduce passes, weight transposes, operand maxima, non-finite guard, per-stream tables
 #pragma once
 #include <cstdlib>
 #include "common.h"
+#include "conv_plan.h"
 
 namespace dadet {
 
@@ -183,14 +189,14 @@ __device__ __forceinline__ void nf_check(const f32x16 (&acc)[TM][TN], unsigned* 
     atomicAdd(flag + 1, 1u);
   }
 }
-// host side (conv_igemm.hip): id of the launch being prepared (recorded in the ring) and the device words
+// host side (conv_aux.hip): id of the launch being prepared (recorded in the ring) and the device words
 unsigned nf_next_launch(const char* kind, int M, int N, int K, int KH);
 unsigned* nf_flag_ptr();
 
 constexpr int PLANE_STRIDE = 40;  // bf16 per staged row: 32 + 8 pad = 80 bytes
 constexpr int EPI_STRIDE = 40;    // floats per transposed row of the 16-byte epilogue
 
-constexpr int BK = 32;          // K-tile
+constexpr int BK = plan::kBK;   // K-tile
 constexpr int LDS_STRIDE = 36;  // floats per staged row (32 + 4 pad, keeps 16-byte alignment)
 
 struct ConvArgs {
@@ -225,7 +231,7 @@ struct ConvArgs {
   // never reset); big_asym != 0 (DADET_BIG_ASYM=1, A/B runs): the round-5 hand-over (part 0 parks everything, part 1 finishes)
   int big_asym;
   // > 0: only the tiles from big_body on (the partly filled last round of a grid of more tiles than CUs) are cut into
-  // big_splits parts; tiles [0, big_body) run their whole reduction in one workgroup (conv_big.hip: big_tail_plan)
+  // big_splits parts; tiles [0, big_body) run their whole reduction in one workgroup (conv_plan.h: big_tail_plan)
   int big_body;
   // non-finite guard (mode 4): device words {first offending launch id + 1, count} and this launch's id; null = off
   unsigned* nf_flag;
@@ -256,7 +262,7 @@ struct WgradArgs {
 };
 
 // several weight gradients in one launch (dadet_conv_wgrad_group): problem i owns workgroups [first[i], first[i + 1])
-constexpr int kWgradGroupMax = 4;
+constexpr int kWgradGroupMax = plan::kGroupMax;
 struct WgradGroup {
   WgradArgs a[kWgradGroupMax];
   int first[kWgradGroupMax + 1];
@@ -264,45 +270,34 @@ struct WgradGroup {
   int by_rows;      // 128 x 128 form: workgroups of one XCD take neighbouring tiles of the same rows
 };
 
-// tile variant chosen for a forward / dgrad GEMM of M rows and Cout columns
-//   0: 128x128 (TM=2,TN=2)   1: 128x64 (TM=2,TN=1)   2: 64x64 (TM=1,TN=1)
-inline int fwd_variant(int M, int Cout) {
-  const int64_t t128 = (int64_t)ceil_div(M, 128) * ceil_div(Cout, 128);
-  // 128x128 tiles from one workgroup per CU on: tools/fwd_sweep.py, res4 3x3 256->256 0.115 ms against 0.128 ms with
-  // 128x64 tiles, res4 1x1 1024->256 0.061 against 0.064 (with two GEMM streams the step did not notice; with one: +0.3%)
-  static const int min_tiles = getenv("DADET_FWD_MIN_TILES128") ? atoi(getenv("DADET_FWD_MIN_TILES128")) : kNumCU;
-  if (Cout > 64 && t128 >= min_tiles) return 0;
-  if (Cout > 32) {
-    const int64_t t64 = (int64_t)ceil_div(M, 128) * ceil_div(Cout, 64);
-    if (t64 >= kNumCU || M <= 64 * 64) return 1;
-    return 2;
-  }
-  return 1;
-}
+static_assert(plan::kCUs == kNumCU, "the plan layer's CU count");
 
 // 4 = products from a 2-term fp16 split of both operands under per-tensor power-of-two scales; 3 / 2 = from a
 // 3- / 2-term bf16 split; 0 = exact fp32 MFMA
 int gemm_mode();
-int launch_fwd_split(ConvArgs& a, int variant, int fmt, hipStream_t st);
+
+// ---- launchers: they launch what the plan says and decide nothing (tiles_m / tiles_n, splits and the scratch pointers are
+// in the argument struct already; the plan carries what selects the kernel)
+int launch_fwd_exact(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st);             // conv_igemm.hip
+int launch_wgrad_exact(WgradArgs& a, hipStream_t st);
+int launch_fwd_split(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st);    // conv_split.hip
 int launch_fwd_split_sk(ConvArgs& a, int fmt, hipStream_t st);
-int launch_wgrad_split(WgradArgs& a, int fmt, hipStream_t st);
-// 256 x 256-tile kernel of mode 4 for the long-K layers (conv_big.hip); ws / counters: split-reduction workspace of
-// big_workspace_bytes(a) bytes and the stream's zeroed counters (may be null when that is 0)
-bool big_eligible(const ConvArgs& a);
-int big_variant(const ConvArgs& a);      // 0 none, 1 the 256 x 256 tile, 2 the 256 x 128 tile
-size_t big_workspace_bytes(const ConvArgs& a);
-int launch_fwd_big(ConvArgs& a, hipStream_t st, float* ws, int* counters);
-// weight gradient on 256 x 256 tiles (conv_big.hip): the plan (false: the 128 x 128 kernel runs) and the launch; partial sums
-// in the 128 x 128 kernel's [splits][Cout][K] layout
-bool wgrad_big_plan(const dadet_conv_desc* d, int* tiles_co, int* tiles_kc, int* splits, int* rps);
+int launch_wgrad_split(WgradArgs& a, bool small_map, int fmt, hipStream_t st);
+int launch_wgrad_split_group(const WgradArgs* a, int n, bool small_map, int by_rows, hipStream_t st);
+int launch_fwd_ws(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st);       // conv_ws.hip
+int launch_fwd_big(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st);               // conv_big.hip
 int launch_wgrad_big(WgradArgs& a, hipStream_t st);
-// several weight gradients in one launch of that kernel (dadet_conv_wgrad_group): membership, the common rows per part, launch
-bool wgrad_group_member(const dadet_conv_desc* d);
-void wgrad_group_plan(int n, const dadet_conv_desc* d, int tile, int* tiles_co, int* tiles_kc, int* splits, int* rows);
 int launch_wgrad_big_group(const WgradArgs* a, int n, hipStream_t st);
-int launch_wgrad_split_group(const WgradArgs* a, int n, hipStream_t st);      // the 128 x 128 kernel's grouped form (conv_split.hip)
-// weight-stationary 1x1 kernel for K = 64 / 128 / 256 (conv_ws.hip)
-bool ws_eligible(const ConvArgs& a);
-int launch_fwd_ws(ConvArgs& a, int fmt, hipStream_t st);
+
+// ---- conv_aux.hip: per-stream tables (contents valid in stream order) and the passes around the GEMMs
+void* stream_scratch(hipStream_t st, size_t bytes);
+int* stream_counters(hipStream_t st);             // plan::kSkCounters zero-initialised words
+unsigned* stream_amax_slots(hipStream_t st);
+hipError_t zero_slots(unsigned* first, int n, hipStream_t st);
+int launch_amax(const float* x, int64_t n, unsigned* slot, hipStream_t st);
+// sums `splits` partial results of a.M x a.Cout floats into a.y under a's epilogue
+int launch_splitk_reduce(const float* partial, int splits, const ConvArgs& a, hipStream_t st);
+int launch_wgrad_reduce(const float* partials, const float* out_scale, float* dw, int Cout, int K, int splits,
+                        int accumulate, hipStream_t st);
 
 }  // namespace dadet

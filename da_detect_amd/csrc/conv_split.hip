@@ -24,9 +24,6 @@
 
 namespace dadet {
 
-static int g_gemm_mode = 4;
-int gemm_mode() { return g_gemm_mode; }
-
 // AB: stage-ablation mask for profiling experiments (tools/ablate.py).  It is a COMPILE-TIME parameter: as run-time
 // branches the checks cut the K loop into a dozen basic blocks and the scheduler could no longer interleave the
 // MFMAs with the split / LDS traffic across them.  Production launches use AB = 0.
@@ -567,11 +564,9 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_split_sk_kernel(const ConvArg
 // DESIGN.md section 6.)
 
 template <int TM, int TN, int FMT, int AB = 0>
-static int launch_split(ConvArgs& a, hipStream_t st) {
+static int launch_split(ConvArgs& a, const int ksplits, hipStream_t st) {
   constexpr int TERMS = Fmt<FMT>::terms;
   constexpr int BM = 2 * TM * 32, BN = 2 * TN * 32;
-  a.tiles_m = ceil_div(a.M, BM);
-  a.tiles_n = ceil_div(a.Cout, BN);
   const size_t lds = sizeof(__bf16) * TERMS * (BM + BN) * PLANE_STRIDE;
   static bool attr_set = false;
   if (!attr_set && lds > 48 * 1024) {
@@ -583,7 +578,6 @@ static int launch_split(ConvArgs& a, hipStream_t st) {
     }
     attr_set = true;
   }
-  const int ksplits = a.ksplit ? ceil_div(a.K, a.ksplit) : 1;
   hipLaunchKernelGGL((conv_fwd_split_kernel<TM, TN, FMT, AB>), dim3(a.tiles_m * a.tiles_n, ksplits), dim3(256), lds,
                      st, a);
   return check_launch("conv_forward(split)");
@@ -608,44 +602,43 @@ static int launch_split_sk(ConvArgs& a, hipStream_t st) {
 }
 
 int launch_fwd_split_sk(ConvArgs& a, int fmt, hipStream_t st) {
-  a.tiles_m = ceil_div(a.M, 128);
-  a.tiles_n = ceil_div(a.Cout, 128);
   return fmt == 4 ? launch_split_sk<4>(a, st) : fmt == 2 ? launch_split_sk<2>(a, st) : launch_split_sk<3>(a, st);
 }
 
-int launch_fwd_split(ConvArgs& a, int variant, int fmt, hipStream_t st) {
-  const int terms = fmt;
+// p.variant picks the tile, p.splits is the number of K ranges (grid.y; a.ksplit elements each)
+int launch_fwd_split(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st) {
+  const int terms = fmt, variant = p.variant, ks = p.splits;
   if (fmt == 4) {
     switch (variant) {
-      case 0: return launch_split<2, 2, 4>(a, st);
-      case 1: return launch_split<2, 1, 4>(a, st);
-      default: return launch_split<1, 1, 4>(a, st);
+      case 0: return launch_split<2, 2, 4>(a, ks, st);
+      case 1: return launch_split<2, 1, 4>(a, ks, st);
+      default: return launch_split<1, 1, 4>(a, ks, st);
     }
   }
   if (a.ablate && variant == 0 && terms == 3) {   // profiling experiments only (DADET_ABLATE)
     switch (a.ablate) {
-      case 1: return launch_split<2, 2, 3, 1>(a, st);
-      case 2: return launch_split<2, 2, 3, 2>(a, st);
-      case 3: return launch_split<2, 2, 3, 3>(a, st);
-      case 8: return launch_split<2, 2, 3, 8>(a, st);
-      case 16: return launch_split<2, 2, 3, 16>(a, st);
-      case 19: return launch_split<2, 2, 3, 19>(a, st);
-      case 23: return launch_split<2, 2, 3, 23>(a, st);
-      case 87: return launch_split<2, 2, 3, 87>(a, st);    // MFMAs only, no barriers either
+      case 1: return launch_split<2, 2, 3, 1>(a, ks, st);
+      case 2: return launch_split<2, 2, 3, 2>(a, ks, st);
+      case 3: return launch_split<2, 2, 3, 3>(a, ks, st);
+      case 8: return launch_split<2, 2, 3, 8>(a, ks, st);
+      case 16: return launch_split<2, 2, 3, 16>(a, ks, st);
+      case 19: return launch_split<2, 2, 3, 19>(a, ks, st);
+      case 23: return launch_split<2, 2, 3, 23>(a, ks, st);
+      case 87: return launch_split<2, 2, 3, 87>(a, ks, st);    // MFMAs only, no barriers either
       default: set_error("conv_forward(split): no kernel compiled for ablation mask %d", a.ablate); return DADET_EINVAL;
     }
   }
   if (terms == 2) {
     switch (variant) {
-      case 0: return launch_split<2, 2, 2>(a, st);
-      case 1: return launch_split<2, 1, 2>(a, st);
-      default: return launch_split<1, 1, 2>(a, st);
+      case 0: return launch_split<2, 2, 2>(a, ks, st);
+      case 1: return launch_split<2, 1, 2>(a, ks, st);
+      default: return launch_split<1, 1, 2>(a, ks, st);
     }
   }
   switch (variant) {
-    case 0: return launch_split<2, 2, 3>(a, st);
-    case 1: return launch_split<2, 1, 3>(a, st);
-    default: return launch_split<1, 1, 3>(a, st);
+    case 0: return launch_split<2, 2, 3>(a, ks, st);
+    case 1: return launch_split<2, 1, 3>(a, ks, st);
+    default: return launch_split<1, 1, 3>(a, ks, st);
   }
 }
 
@@ -939,7 +932,7 @@ static int launch_wgrad_group_terms(const WgradGroup& g, hipStream_t st) {
 }
 
 // contraction mode 4 only; every problem on the same side of the small-map switch (the caller checks)
-int launch_wgrad_split_group(const WgradArgs* a, const int n, hipStream_t st) {
+int launch_wgrad_split_group(const WgradArgs* a, const int n, const bool small_map, const int by_rows, hipStream_t st) {
   WgradGroup g;
   g.n = n;
   int at = 0;
@@ -949,9 +942,8 @@ int launch_wgrad_split_group(const WgradArgs* a, const int n, hipStream_t st) {
     if (i < n) at += a[i].tiles_co * a[i].tiles_kc * a[i].splits;
   }
   g.first[kWgradGroupMax] = at;
-  static const int by_rows = !(getenv("DADET_WGRAD_GROUP_BY_ROWS") && getenv("DADET_WGRAD_GROUP_BY_ROWS")[0] == '0');
   g.by_rows = by_rows;
-  return a[0].Wo < 32 ? launch_wgrad_group_terms<4, true>(g, st) : launch_wgrad_group_terms<4, false>(g, st);
+  return small_map ? launch_wgrad_group_terms<4, true>(g, st) : launch_wgrad_group_terms<4, false>(g, st);
 }
 
 template <int FMT, bool SMALL_MAP>
@@ -973,23 +965,11 @@ static int launch_wgrad_terms(WgradArgs& a, hipStream_t st) {
   return check_launch("conv_wgrad(split)");
 }
 
-int launch_wgrad_split(WgradArgs& a, int terms, hipStream_t st) {
-  const bool small_map = a.Wo < 32;   // narrower than one K-step of rows
+// small_map: output maps narrower than one K-step of rows (Wo < 32)
+int launch_wgrad_split(WgradArgs& a, const bool small_map, int terms, hipStream_t st) {
   if (terms == 4) return small_map ? launch_wgrad_terms<4, true>(a, st) : launch_wgrad_terms<4, false>(a, st);
   if (terms == 2) return small_map ? launch_wgrad_terms<2, true>(a, st) : launch_wgrad_terms<2, false>(a, st);
   return small_map ? launch_wgrad_terms<3, true>(a, st) : launch_wgrad_terms<3, false>(a, st);
 }
 
 }  // namespace dadet
-
-// 4 = 2-term fp16 split under per-tensor power-of-two scales (3 MFMAs / K=16, fp32-class accuracy); 3 = 3-term bf16 split
-// (6 MFMAs / K=16, fp32-class accuracy, no scales); 0 = exact fp32 MFMA; 2 = 2-term bf16 split (3 MFMAs / K=16, ~2^-16)
-extern "C" int dadet_set_gemm_mode(int mode) {
-  if (mode != 0 && mode != 2 && mode != 3 && mode != 4) {
-    dadet::set_error("set_gemm_mode: mode must be 0, 2, 3 or 4");
-    return DADET_EINVAL;
-  }
-  dadet::g_gemm_mode = mode;
-  return DADET_OK;
-}
-extern "C" int dadet_get_gemm_mode(void) { return dadet::g_gemm_mode; }

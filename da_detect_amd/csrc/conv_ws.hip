@@ -350,23 +350,8 @@ __global__ __launch_bounds__(512, 1) void conv1x1_ws_kernel(const ConvArgs a) {
   if (F16 && a.amax_y) amax_publish(a.amax_y, mx);          // once per workgroup: it walked all of its slabs
 }
 
-// panel width per K: the three (FMT 4: two) planes of BN x (K + 8) 16-bit terms plus the epilogue slices (40 KB) must
-// fit 160 KB: 128 columns for K = 64 / 128, 64 for K = 256
-
-bool ws_eligible(const ConvArgs& a) {
-  const char* env = getenv("DADET_WS_1X1");           // read per call: the tests and A/B runs flip it at run time
-  if (env && env[0] == '0') return false;
-  if (a.KH != 1 || a.KW != 1 || a.pad != 0 || a.os != 1 || a.ksplit) return false;
-  if (a.K != 64 && a.K != 128 && a.K != 256) return false;
-  if (!a.epi_v4) return false;                              // 16-byte epilogue: Cout % 4 == 0, aligned tensors
-  if (a.x_bytes >= kOOBws || a.w_bytes >= kOOBws) return false;
-  if (a.Cout < 128 || a.Cout % 32) return false;            // narrow layers stay on the 128 x 64 tiles
-  if (a.M < 64 * WS_ROWS) return false;                     // too few slabs to fill the chip's 256 workgroups
-  return true;
-}
-
 template <int K, int BN, int FMT, int EROWS = 32>
-static int launch_ws(ConvArgs& a, hipStream_t st) {
+static int launch_ws(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st) {
   const size_t lds = (size_t)Fmt<FMT>::terms * BN * (K + 8) * 2 + 8 * EROWS * EPI_STRIDE * 4 + 2 * BN * 4;
   static bool attr_set = false;
   if (!attr_set) {
@@ -378,52 +363,30 @@ static int launch_ws(ConvArgs& a, hipStream_t st) {
     }
     attr_set = true;
   }
-  const int panels_all = ceil_div(a.Cout, BN);
-  a.tiles_m = ceil_div(a.M, WS_ROWS);
-  // one workgroup per CU: `panels` x G with G a multiple of 8 (the XCD mapping above) and at most one slab group per slab
-  const int need = ceil_div(a.tiles_m, 8) * 8;
-  auto groups = [&](const int panels) {
-    int G = (kNumCU / panels) / 8 * 8;
-    if (G < 8) G = 8;
-    return G > need ? need : G;
-  };
-  // A panel count that does not divide the chip (18 panels of the deformable blocks' data gradient, 2304 columns: 18 x 8 =
-  // 144 workgroups walk 8 slabs each) is cut into 2 or 3 launches over column ranges when that shortens the walk: launches
-  // x slabs per workgroup is the launch's length in slab times (9 panels x 24 groups: 2 x 3 instead of 8).
-  int parts = 1, best = ceil_div(a.tiles_m, groups(panels_all));
-  for (int p = 2; p <= 3 && p <= panels_all; ++p) {
-    const int cost = p * ceil_div(a.tiles_m, groups(ceil_div(panels_all, p)));
-    if (cost * 8 < best * 7) { best = cost; parts = p; }      // (at least an eighth shorter: every launch loads its panels anew)
-  }
-  const int per = ceil_div(panels_all, parts);
-  for (int p0 = 0; p0 < panels_all; p0 += per) {
-    a.ws_panel0 = p0;
-    a.tiles_n = panels_all - p0 < per ? panels_all - p0 : per;
-    hipLaunchKernelGGL((conv1x1_ws_kernel<K, BN, FMT, EROWS>), dim3(a.tiles_n * groups(a.tiles_n)), dim3(512), lds, st, a);
+  // 1 - 3 launches over ranges of column panels (conv_plan.h: ws_plan)
+  a.ws_panel0 = 0;
+  for (int i = 0; i < p.ws_parts; ++i) {
+    a.tiles_n = p.ws_panels[i];
+    hipLaunchKernelGGL((conv1x1_ws_kernel<K, BN, FMT, EROWS>), dim3(p.ws_grid[i]), dim3(512), lds, st, a);
+    a.ws_panel0 += p.ws_panels[i];
   }
   return check_launch("conv_forward(weight-stationary 1x1)");
 }
 
-int launch_fwd_ws(ConvArgs& a, int fmt, hipStream_t st) {
+// the kernel instance of the plan's (K, panel width): conv_plan.h picks them
+int launch_fwd_ws(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st) {
+  static_assert(WS_ROWS == plan::kWsRows, "rows per workgroup pass");
   if (fmt == 4) {
-    switch (a.K) {
-      case 64: return launch_ws<64, 128, 4>(a, st);
-      case 128: return launch_ws<128, 128, 4>(a, st);
-      default: {
-        // K = 256: 128-column panels where the layer has at least 256 columns (res4 conv3 and its mirror, 1024 columns:
-        // a workgroup then stores 512 contiguous bytes per row instead of 256, and the activations are read by 8 panels
-        // instead of 16) — the weight planes take 132 KB, the epilogue slices are halved to fit.  DADET_WS_K256_BN=64: off
-        const char* e = getenv("DADET_WS_K256_BN");      // read per call (A/B runs, tests)
-        const bool wide = !(e && atoi(e) == 64);
-        if (wide && a.Cout >= 256) return launch_ws<256, 128, 4, 16>(a, st);
-        return launch_ws<256, 64, 4>(a, st);
-      }
+    switch (p.ws_k) {
+      case 64: return launch_ws<64, 128, 4>(a, p, st);
+      case 128: return launch_ws<128, 128, 4>(a, p, st);
+      default: return p.ws_bn == 128 ? launch_ws<256, 128, 4, 16>(a, p, st) : launch_ws<256, 64, 4>(a, p, st);
     }
   }
-  switch (a.K) {
-    case 64: return launch_ws<64, 128, 3>(a, st);
-    case 128: return launch_ws<128, 128, 3>(a, st);
-    default: return launch_ws<256, 64, 3>(a, st);
+  switch (p.ws_k) {
+    case 64: return launch_ws<64, 128, 3>(a, p, st);
+    case 128: return launch_ws<128, 128, 3>(a, p, st);
+    default: return launch_ws<256, 64, 3>(a, p, st);
   }
 }
 

@@ -171,7 +171,7 @@ int dadet_get_gemm_mode(void);
 
 /* Large-tile kernel of mode 4 (256 x 256 output tile, 8 waves, the two waves of a SIMD alternating between the matrix pipe
  * and the operand staging; csrc/conv_big.hip) for dadet_conv_forward[_scaled] (process-wide):
- *   1 (DEFAULT) = on the layers where it is expected to win (csrc/conv_big.hip: big_variant — K >= 512, M >= 4096,
+ *   1 (DEFAULT) = on the layers where it is expected to win (csrc/conv_plan.h: big_variant — K >= 512, M >= 4096,
  *       Cout >= 128, Cin % 32 == 0, unit output stride, at least 96 output tiles: the 256 x 128-tile variant for
  *       Cout <= 256 — except Cout in (128, 256] with at least 96 row tiles, which fill the chip on the 256 x 256 tile —
  *       the 256 x 256 tile above; everything else stays on the 128 x 128 / weight-stationary kernels);
@@ -219,6 +219,36 @@ int dadet_conv_forward_scaled(const dadet_conv_desc* d, const float* x, const fl
 /* which tile variant dadet_conv_forward launches for this shape: 0 = 128x128 (conv_fwd_kernel<2,2>),
  * 1 = 128x64 (<2,1>), 2 = 64x64 (<1,1>).  Used by bench.py to attribute per-launch timings. */
 int dadet_conv_forward_variant(const dadet_conv_desc* d);
+
+/* The whole plan of a convolution GEMM, as the launch code consumes it (csrc/conv_plan.h; no launch, pure host code).
+ * `family`, forward / data gradient: 0 exact fp32 conv_fwd_kernel, 1 conv_fwd_split_kernel, 2 the same with a stream-K
+ * tail, 3 the same over K ranges + a reduce pass (split-K), 4 weight-stationary 1x1, 5 256 x 256 tile, 6 256 x 128 tile;
+ * weight gradient: 0 exact fp32, 1 128 x 128 split kernel, 2 its small-map form (Wo < 32), 3 256 x 256 tile.
+ * `variant`: what the *_variant query of the same direction answers.  tiles_m / tiles_n: the tile grid (weight gradient:
+ * output-channel tiles, K tiles).  splits: K ranges of split-K (forward) or row ranges (weight gradient, rows_per_split
+ * each).  sk_*: the stream-K tail.  big_splits / big_body: K parts of a large tile / whole-tile workgroups in front of a
+ * tail cut.  launches, grid: GEMM launches (+ the split-K reduce pass) and the workgroups of the first.  workspace_bytes:
+ * forward: scratch the library takes from its per-stream buffer; weight gradient: what the caller must provide.
+ * name: the kernel as profiles label it.  The forward query assumes 16-byte aligned tensors (as torch allocates them).
+ * An empty batch (N == 0) launches nothing: family, variant and name are the label, every number is zero.
+ * One inherited quirk: `variant` and `name` are the label of dadet_conv_forward_variant, which has always assumed the 16-byte
+ * epilogue; under DADET_EPILOGUE_V4=0 (an A/B switch) they keep naming the weight-stationary / large-tile kernel while
+ * family and every number describe the tiled kernel that the launch falls back to. */
+typedef struct dadet_conv_plan_info {
+  int family, variant;
+  int tiles_m, tiles_n;
+  int ksplit, splits;
+  int rows_per_split;
+  int sk_dp_tiles, sk_tiles, sk_units, sk_iters, sk_max_parts;
+  int big_splits, big_body;
+  int launches, grid;
+  int needs_counters;
+  size_t workspace_bytes;
+  char name[64];
+} dadet_conv_plan_info;
+int dadet_conv_forward_plan(const dadet_conv_desc* d, dadet_conv_plan_info* out);
+/* gy_ld: floats between rows of gy (0 = Cout), see dadet_conv_wgrad_partials_ld */
+int dadet_conv_wgrad_plan(const dadet_conv_desc* d, int gy_ld, dadet_conv_plan_info* out);
 
 /* weight gradient: dw[co][r][s][ci] = out_scale[co] * sum_m gy[m][co] * x[gather(m, r, s)][ci]
  * (+ dw_prev when accumulate != 0).  Deterministic split-K over m through `workspace`

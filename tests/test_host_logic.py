@@ -218,7 +218,7 @@ def test_prepare_for_coco_detection_records():
 
 
 def test_weight_gradient_split_plan_respects_the_workgroup_slots():
-    """dadet_conv_wgrad_workspace_bytes is pure host code (the split plan of conv_igemm.hip::wgrad_plan): the number
+    """dadet_conv_wgrad_workspace_bytes is pure host code (the split plan of conv_plan.h::wgrad_plan): the number
     of workgroups (tiles x splits) must not land just above a multiple of the chip's 512 slots — the configuration the
     sweep in profiles/r01_wgrad_split_sweep.txt showed to cost a whole extra pass — and every split keeps >= 4 K-steps"""
     import ctypes
@@ -463,7 +463,7 @@ def test_crowded_images_take_the_unbounded_sampler_path():
 
 
 def test_large_tile_plan_of_the_forward_and_data_gradient_gemms():
-    """csrc/conv_big.hip: big_variant through dadet_conv_forward_variant (no launch): which tile serves a layer under the
+    """csrc/conv_plan.h: big_variant through dadet_conv_forward_variant (no launch): which tile serves a layer under the
     default contraction — 3: weight-stationary (K <= 256 1x1), 4: 256 x 256 tile, 5: 256 x 128 tile, 0 - 2: the 128-wide
     kernels.  Round 6: 129 .. 256 output channels go to the 256 x 256 tile when one column of tiles fills the chip (>= 96 row
     tiles: the pyramid's P2 / P3 layers), and stay on the 256 x 128 tile below that (res4: 64 row tiles)."""

@@ -186,6 +186,31 @@ def nms_with_count(dets, scores, threshold, max_keep=-1, tie_rule=None):
     return keep, count
 
 
+NMS_BATCH_MAX_BOXES = 16384      # per image: the 256-box block sweep's limit (csrc/nms.hip)
+NMS_BATCH_MAX_IMAGES = 64        # the by-value table of per-image counts
+
+
+def nms_batch_with_count(boxes, counts, threshold, max_keep=-1, tie_rule=None, workspace=None):
+    """NMS of a batch of pre-ranked images in one launch per stage (dadet_nms_batch): boxes [B, n_max, 4] best first, counts
+    host ints [B] (image i uses its first counts[i] boxes) -> (keep int64 [B, n_max], num_keep int32 [B]), both on the
+    device, no host sync.  Row i equals nms_with_count(boxes[i, :counts[i]], None, ...)."""
+    _dev(boxes, "boxes")
+    B, n_max = int(boxes.shape[0]), int(boxes.shape[1])
+    boxes = boxes.contiguous()
+    n_host = (ctypes.c_int * max(B, 1))(*[int(c) for c in counts])
+    assert len(counts) == B
+    keep = torch.empty((B, n_max), dtype=torch.int64, device=boxes.device)
+    count = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    if workspace is None:
+        nbytes = ctypes.c_size_t(0)
+        _lib.call("dadet_nms_batch_workspace_bytes", B, n_max, ctypes.byref(nbytes))
+        workspace = _workspace(nbytes.value, boxes.device)
+    rule = NMS_TIE_RULE if tie_rule is None else tie_rule
+    _lib.call("dadet_nms_batch", _p(boxes), n_host, B, n_max, float(threshold), int(rule), int(max_keep), _p(workspace),
+              ctypes.c_size_t(workspace.numel()), _p(keep), _p(count), _stream())
+    return keep, count
+
+
 def nms(dets, scores, threshold):
     """_C.nms(dets[N,4], scores[N], thr) -> int64[K] kept original indices, ascending (nms.h:10-28)."""
     if dets.numel() == 0:
@@ -867,6 +892,42 @@ def da_ins_tail_backward(h, w3, logits, labels, means, coef, inv_keep, r_bce, r_
     return g_z, g_w3, g_b3, g_means
 
 
+def _row_ends(row_end):
+    ends = [int(e) for e in row_end]
+    return (ctypes.c_int * len(ends))(*ends), len(ends)
+
+
+def da_ins_tail_forward_n(h, w3, b3, labels, means, r_bce, r_cst, row_end):
+    """da_ins_tail_forward for len(row_end) images: row_end = ascending ends (host ints) of the images' segments of the
+    consistency rows, row_end[-1] == r_cst; means [L, num_images] | None"""
+    _dev(h, "h")
+    rows, C = h.shape
+    assert rows == r_bce + r_cst
+    L = int(means.shape[0]) if means is not None else 0
+    ends, n_img = _row_ends(row_end)
+    assert means is None or means.shape[1] == n_img
+    logits = torch.empty(rows, dtype=torch.float32, device=h.device)
+    sums = torch.zeros(2, dtype=torch.float32, device=h.device)
+    _lib.call("dadet_da_ins_tail_forward_n", _p(h), _p(w3), _p(b3), _p(labels), _p(means), _p(logits), _p(sums),
+              int(r_bce), int(r_cst), ends, n_img, L, C, _stream())
+    return logits, sums
+
+
+def da_ins_tail_backward_n(h, w3, logits, labels, means, coef, inv_keep, r_bce, r_cst, row_end):
+    """-> (g_z [rows, C], g_w3 [C], g_b3 [1], g_means [L, num_images] | None), as da_ins_tail_backward"""
+    rows, C = h.shape
+    L = int(means.shape[0]) if means is not None else 0
+    ends, n_img = _row_ends(row_end)
+    assert means is None or means.shape[1] == n_img
+    g_z = torch.empty_like(h)
+    acc = torch.zeros(C + 1 + n_img * L, dtype=torch.float32, device=h.device)      # one zero-fill for the three sums
+    g_w3, g_b3 = acc[:C], acc[C:C + 1]
+    g_means = acc[C + 1:].view(L, n_img) if L else None
+    _lib.call("dadet_da_ins_tail_backward_n", _p(h), _p(w3), _p(logits), _p(labels), _p(means), _p(coef), float(inv_keep),
+              _p(g_z), _p(g_w3), _p(g_b3), _p(g_means), int(r_bce), int(r_cst), ends, n_img, L, C, _stream())
+    return g_z, g_w3, g_b3, g_means
+
+
 def da_ins_dropout_rows(h1, masks):
     """h1 [R, C], masks [P, R, C] -> [P * R, C]: the passes' dropped copies of the shared hidden layer"""
     P = masks.shape[0]
@@ -885,11 +946,13 @@ def da_ins_merge(g, masks, h1, grl, need_x=True):
     return g_w, g_x
 
 
-def rpn_decode_clip(deltas_nhwc, anchors, topk_idx, weights, xform_clip, im_w, im_h):
+def rpn_decode_clip(deltas_nhwc, anchors, topk_idx, weights, xform_clip, im_w, im_h, out=None):
     """decode + clip the top-k anchors of ONE image.  deltas_nhwc: [H,W,A*4] (any view whose storage is
-    that order), anchors [H*W*A,4], topk_idx int64[K] -> boxes [K,4]."""
+    that order), anchors [H*W*A,4], topk_idx int64[K] -> boxes [K,4] (written into `out` when given)."""
     K = topk_idx.shape[0]
-    out = torch.empty((K, 4), dtype=torch.float32, device=anchors.device)
+    if out is None:
+        out = torch.empty((K, 4), dtype=torch.float32, device=anchors.device)
+    assert tuple(out.shape) == (K, 4) and out.is_contiguous() and out.dtype == torch.float32
     wx, wy, ww, wh = weights
     _lib.call("dadet_rpn_decode_clip", _p(deltas_nhwc), _p(anchors), _p(topk_idx), K, float(wx), float(wy),
               float(ww), float(wh), float(xform_clip), float(im_w), float(im_h), _p(out), _stream())
@@ -945,9 +1008,11 @@ def da_img_head_loss_backward(t, w2, logits, labels, coef, num_images, rows_per_
 
 
 def triplet_w_forward(a, p, n, margin, eps=1e-6):
-    """a, p, n: [1,C,H,W] channels_last maps -> (loss mean over C*H, dist [H*C,2])"""
+    """a, p, n: [k,C,H,W] channels_last maps -> (loss mean over k*C*H, dist [k*H*C,2]).  A contiguous NHWC batch is the
+    kernel's [k*H][W][C] map: the images' rows follow one another"""
     a, p, n = _nhwc(a), _nhwc(p), _nhwc(n)
-    _, C, H, W = a.shape
+    k, C, H, W = a.shape
+    H = k * H
     dist = torch.empty((H * C, 2), dtype=torch.float32, device=a.device)
     loss_sum = torch.zeros(1, dtype=torch.float32, device=a.device)
     _lib.call("dadet_triplet_w_forward", _p(a), _p(p), _p(n), H, W, C, float(margin), float(eps), _p(dist),
@@ -957,7 +1022,8 @@ def triplet_w_forward(a, p, n, margin, eps=1e-6):
 
 def triplet_w_backward(a, p, n, dist, g_scale, margin, eps=1e-6, need=(True, True, True)):
     a, p, n = _nhwc(a), _nhwc(p), _nhwc(n)
-    _, C, H, W = a.shape
+    k, C, H, W = a.shape
+    H = k * H
     ga = torch.empty_like(a) if need[0] else None
     gp = torch.empty_like(p) if need[1] else None
     gn = torch.empty_like(n) if need[2] else None

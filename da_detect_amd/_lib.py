@@ -77,6 +77,8 @@ _SIGNATURES = {
     "dadet_device_info": [POINTER(c_int), POINTER(c_int), POINTER(c_size_t), c_char_p, c_int],
     "dadet_nms_workspace_bytes": [c_int, POINTER(c_size_t)],
     "dadet_nms": [_P, _P, c_int, c_float, c_int, c_int, _P, c_size_t, _P, _P, _P],
+    "dadet_nms_batch_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],
+    "dadet_nms_batch": [_P, POINTER(c_int), c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P, _P, _P],
     "dadet_roi_align_forward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],
@@ -179,6 +181,9 @@ _SIGNATURES = {
                                           _P, _P, _P],
     "dadet_da_ins_tail_forward": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
     "dadet_da_ins_tail_backward": [_P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P],
+    "dadet_da_ins_tail_forward_n": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, POINTER(c_int), c_int, c_int, c_int, _P],
+    "dadet_da_ins_tail_backward_n": [_P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P, c_int, c_int, POINTER(c_int), c_int,
+                                     c_int, c_int, _P],
     "dadet_da_ins_dropout_rows": [_P, _P, _P, c_int64, c_int, _P],
     "dadet_da_ins_merge": [_P, _P, _P, _P, _P, _P, c_int64, c_int, _P],
     "dadet_triplet_w_forward": [_P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P],

@@ -345,6 +345,148 @@ __global__ __launch_bounds__(256) void da_ins_bwd_kernel(const float* __restrict
   if (threadIdx.x == 0 && s_m[2 * L] != 0.f) atomicAdd(g_b3, s_m[2 * L]);
 }
 
+// ---- the same tail for any number of images --------------------------------------------------------
+// Consistency rows are stacked image by image; image i owns rows [row_end[i-1], row_end[i]) of the R_cst consistency rows
+// (an image may own none).  The ends are known on the host and travel BY VALUE with the launch (no device buffer, no copy);
+// the workgroup keeps them in LDS and every wavefront finds its row's image from them: its rows ascend, so the image index
+// only ever moves forward.  means / g_means are [L][num_images].  Everything else — one wavefront per row, float4 along
+// the hidden units, the fixed order of the forward sums, the LDS accumulators of the backward — is da_ins_fwd_kernel /
+// da_ins_bwd_kernel, and for two images with ends {n_src, R_cst} the forward gives the same bits.
+constexpr int kDaInsMaxImg = 64;         // images per launch (the by-value table of segment ends)
+constexpr int kDaInsMaxMeans = 512;      // levels x images whose gradient sums the backward keeps in LDS
+struct DaRowEnds {
+  int end[kDaInsMaxImg];
+};
+
+__global__ __launch_bounds__(256) void da_ins_fwd_n_kernel(const float* __restrict__ h, const float* __restrict__ w3,
+                                                           const float* __restrict__ b3,
+                                                           const float* __restrict__ labels,
+                                                           const float* __restrict__ means, float* __restrict__ logits,
+                                                           float* __restrict__ sums, float* __restrict__ partials,
+                                                           int R_bce, int R_cst, DaRowEnds ends, int NI, int L, int C) {
+  __shared__ float s_acc[4][2];
+  __shared__ int s_end[kDaInsMaxImg];
+  if (threadIdx.x < NI) s_end[threadIdx.x] = ends.end[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int R = R_bce + R_cst;
+  const float bias = b3[0];
+  float bce = 0.f, cst = 0.f;
+  int img = 0;
+  for (int r = wave_global; r < R; r += nwaves) {
+    const float* row = h + (size_t)r * C;
+    float dot = 0.f;
+    for (int c = lane * 4; c < C; c += 256) {
+      const float4 hv = *reinterpret_cast<const float4*>(row + c);
+      const float4 wv = *reinterpret_cast<const float4*>(w3 + c);
+      dot += hv.x * wv.x + hv.y * wv.y + hv.z * wv.z + hv.w * wv.w;
+    }
+    const float logit = wave_sum(dot) + bias;
+    if (r >= R_bce)
+      while (img < NI - 1 && (r - R_bce) >= s_end[img]) ++img;     // wave-uniform; the host checked end[NI - 1] == R_cst
+    if (lane == 0) {
+      logits[r] = logit;
+      if (r < R_bce) {
+        bce += bce_with_logits(logit, labels[r]);
+      } else {
+        const float sg = sigmoidf(logit);
+        for (int l = 0; l < L; ++l) cst += fabsf(means[l * NI + img] - sg);
+      }
+    }
+  }
+  if (lane == 0) {
+    s_acc[wave][0] = bce;
+    s_acc[wave][1] = cst;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const float v = ((s_acc[0][threadIdx.x] + s_acc[1][threadIdx.x]) + s_acc[2][threadIdx.x]) + s_acc[3][threadIdx.x];
+    if (partials) partials[(size_t)blockIdx.x * 2 + threadIdx.x] = v;
+    else if (v != 0.f) atomicAdd(&sums[threadIdx.x], v);
+  }
+}
+
+// LDS: [C] workgroup partial of g_w3, [L * NI] of g_means, [1] of g_b3
+__global__ __launch_bounds__(256) void da_ins_bwd_n_kernel(const float* __restrict__ h, const float* __restrict__ w3,
+                                                           const float* __restrict__ logits,
+                                                           const float* __restrict__ labels,
+                                                           const float* __restrict__ means,
+                                                           const float* __restrict__ coef, float inv_keep,
+                                                           float* __restrict__ g_z, float* __restrict__ g_w3,
+                                                           float* __restrict__ g_b3, float* __restrict__ g_means,
+                                                           int R_bce, int R_cst, DaRowEnds ends, int NI, int L, int C) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ int s_end[kDaInsMaxImg];
+  float* s_w = reinterpret_cast<float*>(smem);
+  float* s_m = s_w + C;
+  const int LM = L * NI;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nw_block = blockDim.x >> 6;
+  for (int c = threadIdx.x; c < C + LM + 1; c += blockDim.x) s_w[c] = 0.f;
+  if (threadIdx.x < NI) s_end[threadIdx.x] = ends.end[threadIdx.x];
+  __syncthreads();
+  const int R = R_bce + R_cst;
+  const float a_bce = coef[0], a_cst = coef[1];
+  float4 wacc[4];     // C <= 1024: lane owns float4 slots c = lane*4 + 256*k
+#pragma unroll
+  for (int k = 0; k < 4; ++k) wacc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float bacc = 0.f;
+  int img = 0;
+  for (int r = blockIdx.x * nw_block + wave; r < R; r += gridDim.x * nw_block) {
+    const float sg = sigmoidf(logits[r]);
+    float dl;
+    if (r < R_bce) {
+      dl = a_bce * (sg - labels[r]);
+    } else {
+      while (img < NI - 1 && (r - R_bce) >= s_end[img]) ++img;
+      float sgn = 0.f;    // d |m - s| / d s summed over levels
+      for (int l = 0; l < L; ++l) {
+        const float d = means[l * NI + img] - sg;
+        const float sd = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        sgn -= sd;
+        if (lane == 0 && sd != 0.f) atomicAdd(&s_m[l * NI + img], a_cst * sd);
+      }
+      dl = a_cst * sgn * sg * (1.f - sg);
+    }
+    bacc += dl;
+    const float* row = h + (size_t)r * C;
+    const float gk = dl * inv_keep;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = lane * 4 + 256 * k;
+      if (c < C) {
+        const float4 hv = *reinterpret_cast<const float4*>(row + c);
+        const float4 wv = *reinterpret_cast<const float4*>(w3 + c);
+        float4 o;
+        o.x = hv.x != 0.f ? gk * wv.x : 0.f; o.y = hv.y != 0.f ? gk * wv.y : 0.f;
+        o.z = hv.z != 0.f ? gk * wv.z : 0.f; o.w = hv.w != 0.f ? gk * wv.w : 0.f;
+        *reinterpret_cast<float4*>(g_z + (size_t)r * C + c) = o;
+        wacc[k].x += dl * hv.x; wacc[k].y += dl * hv.y; wacc[k].z += dl * hv.z; wacc[k].w += dl * hv.w;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = lane * 4 + 256 * k;
+    if (c < C) {
+      atomicAdd(&s_w[c + 0], wacc[k].x);
+      atomicAdd(&s_w[c + 1], wacc[k].y);
+      atomicAdd(&s_w[c + 2], wacc[k].z);
+      atomicAdd(&s_w[c + 3], wacc[k].w);
+    }
+  }
+  if (lane == 0 && bacc != 0.f) atomicAdd(&s_m[LM], bacc);   // bacc is wavefront-uniform
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += blockDim.x)
+    if (s_w[c] != 0.f) atomicAdd(&g_w3[c], s_w[c]);
+  if (g_means)
+    for (int i = threadIdx.x; i < LM; i += blockDim.x)
+      if (s_m[i] != 0.f) atomicAdd(&g_means[i], s_m[i]);
+  if (threadIdx.x == 0 && s_m[LM] != 0.f) atomicAdd(g_b3, s_m[LM]);
+}
+
 // the two passes share the head's first layer up to its dropout mask: h1s = [h1 * mask_a; h1 * mask_b]
 __global__ __launch_bounds__(256) void da_ins_dropout_rows_kernel(const float4* __restrict__ h1,
                                                                   const float4* __restrict__ masks,
@@ -612,6 +754,67 @@ extern "C" int dadet_da_ins_tail_backward(const float* h, const float* w3, const
                      h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3, g_means, R_bce, R_cst, n_src, levels,
                      C);
   return check_launch("da_ins_tail_backward");
+}
+
+// the segment ends of the `_n` entry points: host array -> by-value table; false when they are not a non-decreasing walk
+// from >= 0 to R_cst
+static bool da_row_ends(const int* row_end, int num_images, int R_cst, DaRowEnds* out) {
+  int prev = 0;
+  for (int i = 0; i < num_images; ++i) {
+    if (row_end[i] < prev) return false;
+    out->end[i] = prev = row_end[i];
+  }
+  for (int i = num_images; i < kDaInsMaxImg; ++i) out->end[i] = prev;
+  return prev == R_cst;
+}
+
+extern "C" int dadet_da_ins_tail_forward_n(const float* h, const float* w3, const float* b3, const float* labels,
+                                           const float* means, float* logits, float* sums, int R_bce, int R_cst,
+                                           const int* row_end, int num_images, int levels, int C, void* stream) {
+  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && levels >= 0, "da_ins_tail_forward_n: bad dims");
+  DADET_REQUIRE(num_images >= 1 && num_images <= kDaInsMaxImg && row_end,
+                "da_ins_tail_forward_n: num_images must be in 1..64, with its row segment ends");
+  DaRowEnds ends;
+  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends),
+                "da_ins_tail_forward_n: row_end must ascend from >= 0 and end at R_cst");
+  if (R_bce + R_cst == 0) return DADET_OK;
+  DADET_REQUIRE(h && w3 && b3 && logits && sums && a16(h) && a16(w3) && (R_bce == 0 || labels) &&
+                    (R_cst == 0 || (means && levels > 0)),
+                "da_ins_tail_forward_n: bad pointers");
+  int blocks = ceil_div(R_bce + R_cst, 4);
+  if (blocks > kNumCU * 2) blocks = kNumCU * 2;
+  float* partials = da_partials(as_stream(stream));
+  hipLaunchKernelGGL(da_ins_fwd_n_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), h, w3, b3, labels, means,
+                     logits, sums, partials, R_bce, R_cst, ends, num_images, levels, C);
+  if (partials)
+    hipLaunchKernelGGL(da_partials_sum_kernel, dim3(2), dim3(256), 0, as_stream(stream), partials, blocks, 2, sums);
+  return check_launch("da_ins_tail_forward_n");
+}
+
+extern "C" int dadet_da_ins_tail_backward_n(const float* h, const float* w3, const float* logits, const float* labels,
+                                            const float* means, const float* coef, float inv_keep, float* g_z,
+                                            float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst,
+                                            const int* row_end, int num_images, int levels, int C, void* stream) {
+  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && C <= 1024 && levels >= 0 && levels <= 16,
+                "da_ins_tail_backward_n: C must be a multiple of 4 and <= 1024, levels <= 16");
+  DADET_REQUIRE(num_images >= 1 && num_images <= kDaInsMaxImg && row_end,
+                "da_ins_tail_backward_n: num_images must be in 1..64, with its row segment ends");
+  DADET_REQUIRE(levels * num_images <= kDaInsMaxMeans,
+                "da_ins_tail_backward_n: levels x num_images exceeds the 512 sums kept in LDS");
+  DaRowEnds ends;
+  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends),
+                "da_ins_tail_backward_n: row_end must ascend from >= 0 and end at R_cst");
+  if (R_bce + R_cst == 0) return DADET_OK;
+  DADET_REQUIRE(h && w3 && logits && coef && g_z && g_w3 && g_b3 && a16(h) && a16(w3) && a16(g_z) &&
+                    (R_bce == 0 || labels) && (R_cst == 0 || (means && levels > 0)),
+                "da_ins_tail_backward_n: bad pointers");
+  int blocks = ceil_div(R_bce + R_cst, 4 * 4);
+  if (blocks > kNumCU) blocks = kNumCU;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(da_ins_bwd_n_kernel, dim3(blocks), dim3(256), sizeof(float) * (C + levels * num_images + 1),
+                     as_stream(stream), h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3, g_means, R_bce,
+                     R_cst, ends, num_images, levels, C);
+  return check_launch("da_ins_tail_backward_n");
 }
 
 extern "C" int dadet_da_ins_dropout_rows(const float* h1, const float* masks, float* out, int64_t numel_per_pass,

@@ -136,15 +136,15 @@ __device__ __forceinline__ bool iou_suppresses(const float inter, const float u,
   return (TIE_RULE == 0) ? (ovr >= thresh) : (ovr > thresh);
 }
 
+// (the body of nms_mask_kernel and nms_mask_batch_kernel: one 64-thread workgroup, tile (row_start, col_start) of one image)
 template <int TIE_RULE>
-__global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__ sorted, int n,
-                                                      float thresh, int col_blocks,
-                                                      unsigned long long* __restrict__ mask,
-                                                      unsigned long long* __restrict__ diag_t,
-                                                      unsigned long long* __restrict__ adj_t,
-                                                      unsigned long long* __restrict__ blk_t) {
-  // linear block id -> (row_block <= col_block) pair
-  const int row_start = blockIdx.y, col_start = blockIdx.x;
+__device__ __forceinline__ void nms_mask_body(const float4* __restrict__ sorted, const int n, const float thresh,
+                                              const int col_blocks, unsigned long long* __restrict__ mask,
+                                              unsigned long long* __restrict__ diag_t,
+                                              unsigned long long* __restrict__ adj_t,
+                                              unsigned long long* __restrict__ blk_t, const int row_start,
+                                              const int col_start) {
+  // (row_block <= col_block) pairs only
   if (col_start < row_start) return;
   // blk_t (nms_sweep_block_kernel): per box eight words — which boxes of the PREVIOUS 256-box block (words 0 - 3) and of
   // its OWN block before it (words 4 - 7) suppress it; row chunks 4 (B - 1) .. c of column chunk c (B = c / 4) fill them,
@@ -212,6 +212,16 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__
     }
     mask[(size_t)cur * col_blocks + col_start] = t;
   }
+}
+
+template <int TIE_RULE>
+__global__ __launch_bounds__(64) void nms_mask_kernel(const float4* __restrict__ sorted, int n,
+                                                      float thresh, int col_blocks,
+                                                      unsigned long long* __restrict__ mask,
+                                                      unsigned long long* __restrict__ diag_t,
+                                                      unsigned long long* __restrict__ adj_t,
+                                                      unsigned long long* __restrict__ blk_t) {
+  nms_mask_body<TIE_RULE>(sorted, n, thresh, col_blocks, mask, diag_t, adj_t, blk_t, blockIdx.y, blockIdx.x);
 }
 
 // ---- greedy sweep, one workgroup ------------------------------------------------------------
@@ -482,10 +492,11 @@ __global__ __launch_bounds__(256) void nms_sweep_pipelined_kernel(const unsigned
 // 12 000 boxes with a quota of 2000, mask kernel included) — what bounds them is not the resolution but the chain "resolve a
 // block -> fetch its kept rows (1.5 KB each, ~3 MB per NMS, HBM latency, one workgroup: ~50 GB/s) -> two blocks later";
 // inside the training step, beside the GEMM waves, fewer barriers are worth 0.03 (img_only) to 0.07 ms (da).
-__global__ __launch_bounds__(256) void nms_sweep_block_kernel(const unsigned long long* __restrict__ mask,
-                                                              const unsigned long long* __restrict__ blk_t, int n,
-                                                              int col_blocks, int max_keep,
-                                                              unsigned long long* __restrict__ keep_bits) {
+// (the body of nms_sweep_block_kernel and nms_sweep_block_batch_kernel: one 256-thread workgroup, one image, n >= 1)
+__device__ __forceinline__ void nms_sweep_block_body(const unsigned long long* __restrict__ mask,
+                                                     const unsigned long long* __restrict__ blk_t, const int n,
+                                                     const int col_blocks, const int max_keep,
+                                                     unsigned long long* __restrict__ keep_bits) {
   // (a block of 256 boxes keeps ~40 where 64-box chunks keep ~10: with 24 slots the rest of every block was fetched
   // synchronously, one exposed HBM round trip per block)
   constexpr int kSlots = 48;
@@ -606,6 +617,13 @@ __global__ __launch_bounds__(256) void nms_sweep_block_kernel(const unsigned lon
   if (w < col_blocks) keep_bits[w] = s_keep_all[w];
 }
 
+__global__ __launch_bounds__(256) void nms_sweep_block_kernel(const unsigned long long* __restrict__ mask,
+                                                              const unsigned long long* __restrict__ blk_t, int n,
+                                                              int col_blocks, int max_keep,
+                                                              unsigned long long* __restrict__ keep_bits) {
+  nms_sweep_block_body(mask, blk_t, n, col_blocks, max_keep, keep_bits);
+}
+
 // ---- compaction to ascending original indices ----------------------------------------------
 __global__ void nms_flag_kernel(const unsigned long long* __restrict__ keep_bits,
                                 const int* __restrict__ order, int n, unsigned char* __restrict__ flag) {
@@ -645,9 +663,9 @@ __global__ __launch_bounds__(64) void nms_compact_kernel(const unsigned char* __
 // Pre-ranked input (the RPN hands its boxes over in score order and wants positions in THAT order back): the kept
 // positions ascend with the keep words, so the flag pass + the one-wave compaction (5 + 22 us on the path between the sweep
 // and the box head) are one small kernel — thread w counts word w, an LDS scan gives its first slot, it writes its bits.
-__global__ __launch_bounds__(256) void nms_compact_bits_kernel(const unsigned long long* __restrict__ keep_bits,
-                                                               int col_blocks, int64_t* __restrict__ keep_out,
-                                                               int* __restrict__ num_out) {
+__device__ __forceinline__ void nms_compact_bits_body(const unsigned long long* __restrict__ keep_bits,
+                                                      const int col_blocks, int64_t* __restrict__ keep_out,
+                                                      int* __restrict__ num_out) {
   __shared__ int s_scan[256];
   const int w = threadIdx.x;
   unsigned long long bits = w < col_blocks ? keep_bits[w] : 0ULL;
@@ -667,6 +685,62 @@ __global__ __launch_bounds__(256) void nms_compact_bits_kernel(const unsigned lo
     bits &= bits - 1ULL;
   }
   if (w == 255) *num_out = s_scan[255];
+}
+
+__global__ __launch_bounds__(256) void nms_compact_bits_kernel(const unsigned long long* __restrict__ keep_bits,
+                                                               int col_blocks, int64_t* __restrict__ keep_out,
+                                                               int* __restrict__ num_out) {
+  nms_compact_bits_body(keep_bits, col_blocks, keep_out, num_out);
+}
+
+// ---- a batch of pre-ranked images: the three stages above with the image taken from a grid dimension ---------------
+// Independent images are independent workgroups: the sweep of one image is one workgroup bound by the latency of its chain
+// (see nms_sweep_block_kernel), so several of them overlap on different CUs instead of queueing one behind the other.  The
+// per-image box counts are known on the host and travel by value with the launch; image i works in its own slice of the
+// workspace (stride: the layout of n_max boxes) exactly as a single-image call with n = n[i] would in its own workspace —
+// same device bodies, same arguments, hence the same keep bits.
+constexpr int kNmsMaxBatch = 64;
+struct NmsBatchCounts {
+  int n[kNmsMaxBatch];
+};
+struct NmsBatchLayout {      // byte offsets inside one image's slice (nms_layout of n_max) and the slice stride
+  size_t mask_off, keepbits_off, blkt_off, adjt_off, stride;
+};
+
+template <int TIE_RULE>
+__global__ __launch_bounds__(64) void nms_mask_batch_kernel(const float4* __restrict__ boxes, NmsBatchCounts counts,
+                                                            int n_max, float thresh, char* __restrict__ workspace,
+                                                            NmsBatchLayout lay) {
+  const int img = blockIdx.z;
+  const int n = counts.n[img];
+  const int col_blocks = (n + 63) >> 6;
+  if ((int)blockIdx.x >= col_blocks || (int)blockIdx.y >= col_blocks) return;
+  char* base = workspace + (size_t)img * lay.stride;
+  nms_mask_body<TIE_RULE>(boxes + (size_t)img * n_max, n, thresh, col_blocks,
+                          reinterpret_cast<unsigned long long*>(base + lay.mask_off), nullptr,
+                          reinterpret_cast<unsigned long long*>(base + lay.adjt_off),
+                          reinterpret_cast<unsigned long long*>(base + lay.blkt_off), blockIdx.y, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void nms_sweep_block_batch_kernel(NmsBatchCounts counts, int max_keep,
+                                                                    char* __restrict__ workspace, NmsBatchLayout lay) {
+  const int img = blockIdx.x;
+  const int n = counts.n[img];
+  if (n == 0) return;                  // (nothing to keep; the compaction below reads no keep word of an empty image)
+  char* base = workspace + (size_t)img * lay.stride;
+  nms_sweep_block_body(reinterpret_cast<const unsigned long long*>(base + lay.mask_off),
+                       reinterpret_cast<const unsigned long long*>(base + lay.blkt_off), n, (n + 63) >> 6, max_keep,
+                       reinterpret_cast<unsigned long long*>(base + lay.keepbits_off));
+}
+
+__global__ __launch_bounds__(256) void nms_compact_bits_batch_kernel(NmsBatchCounts counts, int n_max,
+                                                                     const char* __restrict__ workspace,
+                                                                     NmsBatchLayout lay, int64_t* __restrict__ keep_out,
+                                                                     int* __restrict__ num_out) {
+  const int img = blockIdx.x;
+  const int n = counts.n[img];
+  nms_compact_bits_body(reinterpret_cast<const unsigned long long*>(workspace + (size_t)img * lay.stride + lay.keepbits_off),
+                        (n + 63) >> 6, keep_out + (size_t)img * n_max, num_out + img);
 }
 
 static int next_pow2(int n) {
@@ -798,4 +872,59 @@ extern "C" int dadet_nms(const float* boxes_xyxy, const float* scores, int n, fl
     hipLaunchKernelGGL(nms_compact_kernel, dim3(1), dim3(64), 0, st, flag, n, keep_out, num_keep_out);
   }
   return check_launch("nms");
+}
+
+extern "C" int dadet_nms_batch_workspace_bytes(int batch, int n_max, size_t* bytes_out) {
+  DADET_REQUIRE(batch >= 0 && n_max >= 0 && bytes_out, "nms_batch_workspace_bytes: bad args");
+  *bytes_out = (batch == 0 || n_max == 0) ? 0 : (size_t)batch * nms_layout(n_max).total;
+  return DADET_OK;
+}
+
+extern "C" int dadet_nms_batch(const float* boxes_xyxy, const int* n_host, int batch, int n_max, float thresh, int tie_rule,
+                               int max_keep, void* workspace, size_t workspace_bytes, int64_t* keep_out,
+                               int* num_keep_out, void* stream) {
+  DADET_REQUIRE(batch >= 0 && batch <= kNmsMaxBatch && n_max >= 0, "nms_batch: batch must be in 0..%d, n_max >= 0",
+                kNmsMaxBatch);
+  if (batch == 0) return DADET_OK;
+  DADET_REQUIRE(n_host && num_keep_out, "nms_batch: null pointer");
+  DADET_REQUIRE(tie_rule == 0 || tie_rule == 1, "nms_batch: tie_rule must be 0 (>=) or 1 (>)");
+  // the block sweep and the one-workgroup compaction hold 256 keep words: 16 384 boxes per image
+  DADET_REQUIRE(n_max <= 256 * 64, "nms_batch: n_max=%d exceeds the block sweep's 16384 boxes per image", n_max);
+  NmsBatchCounts counts;
+  int n_top = 0;
+  for (int i = 0; i < kNmsMaxBatch; ++i) {
+    counts.n[i] = i < batch ? n_host[i] : 0;
+    DADET_REQUIRE(counts.n[i] >= 0 && counts.n[i] <= n_max, "nms_batch: n[%d]=%d outside 0..n_max=%d", i, counts.n[i], n_max);
+    if (counts.n[i] > n_top) n_top = counts.n[i];
+  }
+  hipStream_t st = as_stream(stream);
+  if (n_top == 0) {
+    (void)hipMemsetAsync(num_keep_out, 0, sizeof(int) * (size_t)batch, st);
+    return check_launch("nms_batch(empty)");
+  }
+  DADET_REQUIRE(boxes_xyxy && keep_out && workspace, "nms_batch: null pointer");
+  DADET_REQUIRE((reinterpret_cast<uintptr_t>(boxes_xyxy) & 15) == 0, "nms_batch: boxes must be 16-byte aligned");
+  const NmsWorkspace ws = nms_layout(n_max);
+  if (workspace_bytes < (size_t)batch * ws.total) {
+    set_error("nms_batch: workspace %zu < required %zu", workspace_bytes, (size_t)batch * ws.total);
+    return DADET_EWORKSPACE;
+  }
+  NmsBatchLayout lay;
+  lay.mask_off = ws.mask_off;
+  lay.keepbits_off = ws.keepbits_off;
+  lay.blkt_off = ws.blkt_off;
+  lay.adjt_off = ws.adjt_off;
+  lay.stride = ws.total;
+  char* base = static_cast<char*>(workspace);
+  const float4* boxes = reinterpret_cast<const float4*>(boxes_xyxy);
+  const int cb = ceil_div(n_top, 64);
+  const dim3 mgrid(cb, cb, batch);
+  if (tie_rule == 0)
+    hipLaunchKernelGGL(nms_mask_batch_kernel<0>, mgrid, dim3(64), 0, st, boxes, counts, n_max, thresh, base, lay);
+  else
+    hipLaunchKernelGGL(nms_mask_batch_kernel<1>, mgrid, dim3(64), 0, st, boxes, counts, n_max, thresh, base, lay);
+  hipLaunchKernelGGL(nms_sweep_block_batch_kernel, dim3(batch), dim3(256), 0, st, counts, max_keep, base, lay);
+  hipLaunchKernelGGL(nms_compact_bits_batch_kernel, dim3(batch), dim3(256), 0, st, counts, n_max, base, lay, keep_out,
+                     num_keep_out);
+  return check_launch("nms_batch");
 }

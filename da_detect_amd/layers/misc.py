@@ -293,19 +293,30 @@ fast_rcnn_loss_rows_fused = _FastRCNNLossRows.apply
 fast_rcnn_loss_fused = _FastRCNNLoss.apply
 
 
-def consistency_loss(img_feas, ins_fea, ins_labels, size_average=True):
+def consistency_loss(img_feas, ins_fea, ins_labels, size_average=True, rows_per_image=None):
     """|mean_hw(p_img_i) - p_ins_ij| (layers/consistency_loss.py:3-27).  `img_feas` is a list of per-level
-    [N,1,H,W] probability maps, or (fused path) of per-level [N] tensors that already hold the spatial mean."""
+    [N,1,H,W] probability maps, or (fused path) of per-level [N] tensors that already hold the spatial mean.
+    `rows_per_image` (host ints, one per image, rows stacked in image order): the docstring formula of the reference for any
+    N, every ROI against the mean of its own image; without it the reference's N == 2 form, source rows first."""
     loss = []
-    n_src = getattr(ins_labels, "_n_src_host", None)   # set by the box head, which knows it without a round trip
-    if n_src is None:
-        n_src = int(torch.nonzero(ins_labels).size(0))
-    intervals = [n_src, ins_fea.size(0) - n_src]
+    if rows_per_image is None:
+        n_src = getattr(ins_labels, "_n_src_host", None)   # set by the box head, which knows it without a round trip
+        if n_src is None:
+            n_src = int(torch.nonzero(ins_labels).size(0))
+        intervals = [n_src, ins_fea.size(0) - n_src]
+    else:
+        intervals = [int(r) for r in rows_per_image]
+        if sum(intervals) != ins_fea.size(0) or min(intervals) < 0:
+            raise ValueError("consistency loss: rows_per_image {} does not describe {} rows".format(
+                intervals, ins_fea.size(0)))
     for lvl in img_feas:
         means = lvl if lvl.dim() == 1 else torch.mean(lvl.reshape(lvl.shape[0], -1), 1)
-        assert means.shape[0] == 2, \
-            "only batch size=2 is supported for consistency loss now, received batch size: {}".format(means.shape[0])
-        rows = torch.cat([means[i].view(1, 1).repeat(intervals[i], 1) for i in range(2)], dim=0)
+        if rows_per_image is None:
+            assert means.shape[0] == 2, \
+                "only batch size=2 is supported for consistency loss now, received batch size: {}".format(means.shape[0])
+        elif means.shape[0] != len(intervals):
+            raise ValueError("consistency loss: {} images, rows_per_image of {}".format(means.shape[0], len(intervals)))
+        rows = torch.cat([means[i].view(1, 1).repeat(intervals[i], 1) for i in range(len(intervals))], dim=0)
         loss.append(torch.abs(rows - ins_fea))
     loss = torch.cat(loss, dim=1)
     return loss.mean() if size_average else loss.sum()

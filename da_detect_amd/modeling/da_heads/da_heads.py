@@ -111,6 +111,23 @@ def _n_source_rows(da_ins_labels):
     return int(torch.nonzero(da_ins_labels).size(0)) if n_src is None else int(n_src)
 
 
+def _rows_per_image(da_ins_labels, means):
+    """rows of each image among the instance rows (set by the box head, host ints) for the consistency term; None for the
+    reference's batch [source, target], whose split is _n_source_rows.  `means` [levels, images] or None"""
+    rows = getattr(da_ins_labels, "_rows_per_image_host", None)
+    if means is None:
+        return None
+    if rows is None:
+        if means.shape[1] != 2:
+            raise ValueError("consistency loss over {} images needs the per-image row counts of the box head "
+                             "(da_ins_labels._rows_per_image_host)".format(means.shape[1]))
+        return None
+    if len(rows) != means.shape[1]:
+        raise ValueError("consistency loss: instance rows of {} images, image-level means of {}".format(
+            len(rows), means.shape[1]))
+    return rows
+
+
 def _vector_ins_features(cfg):
     """True when the box head already yields one vector per ROI.  The reference tests CONV_BODY.startswith('V')
     (da_heads.py:367-369); its FPN combination was never wired (AvgPool2d on the FPN2MLP vector and a 2048-wide
@@ -243,8 +260,8 @@ class DomainAdaptationModule(torch.nn.Module):
         if self.ins_weight > 0:
             losses["loss_da_instance"] = self.ins_weight * da_ins_loss(da_ins_features, da_ins_labels)
         if self.cst_weight > 0:
-            losses["loss_da_consistency"] = self.cst_weight * da_consist_loss(img_mean_sig, da_ins_consist,
-                                                                              da_ins_labels)
+            losses["loss_da_consistency"] = self.cst_weight * da_consist_loss(
+                img_mean_sig, da_ins_consist, da_ins_labels, getattr(da_ins_labels, "_rows_per_image_host", None))
         return losses
 
     def _forward_fused_instance(self, img_features, feat, da_ins_labels, targets, early):
@@ -270,12 +287,10 @@ class DomainAdaptationModule(torch.nn.Module):
             return losses
         if len(sel) == 1:
             masks1, masks2 = masks1[sel[0]:sel[0] + 1], masks2[sel[0]:sel[0] + 1]
-        means = torch.stack(list(img_mean_sig)) if self.cst_weight > 0 else None        # [levels, 2]
-        if means is not None:
-            assert means.shape[1] == 2, \
-                "only batch size=2 is supported for consistency loss now, received batch size: {}".format(means.shape[1])
+        means = torch.stack(list(img_mean_sig)) if self.cst_weight > 0 else None        # [levels, images]
         bce, cst, _ = da_instance_head(feat, self.inshead, da_ins_labels, means, masks1, masks2,
-                                       _grl_vector(grl, feat.device), kinds, _n_source_rows(da_ins_labels))
+                                       _grl_vector(grl, feat.device), kinds, _n_source_rows(da_ins_labels),
+                                       _rows_per_image(da_ins_labels, means))
         if self.ins_weight > 0:
             losses["loss_da_instance"] = self.ins_weight * bce
         if self.cst_weight > 0:
@@ -375,8 +390,8 @@ class DomainAdaptationModule_triplet(torch.nn.Module):
         if self.cst_weight > 0:
             feat = _pool_ins(da_ins_feature, self.resnet_backbone)
             ins_consist = self.inshead(self.grl_ins_consist(feat)).sigmoid()
-            losses["loss_da_consistency"] = self.cst_weight * da_consist_loss(img_mean_sig, ins_consist,
-                                                                              da_ins_labels)
+            losses["loss_da_consistency"] = self.cst_weight * da_consist_loss(
+                img_mean_sig, ins_consist, da_ins_labels, getattr(da_ins_labels, "_rows_per_image_host", None))
         return losses
 
 
@@ -433,10 +448,8 @@ def _triplet_fused_instance_losses(self, feat, da_ins_labels, img_mean_sig):
     means = None
     if self.cst_weight > 0:
         means = torch.stack(list(img_mean_sig) if isinstance(img_mean_sig, (list, tuple)) else [img_mean_sig])
-        assert means.shape[1] == 2, \
-            "only batch size=2 is supported for consistency loss now, received batch size: {}".format(means.shape[1])
     bce, cst, _ = da_instance_head(feat, self.inshead, da_ins_labels, means, masks1, masks2, _grl_vector(grl, dev), kinds,
-                                   n_src)
+                                   n_src, _rows_per_image(da_ins_labels, means))
     out = {}
     if self.ins_weight > 0:
         out["loss_da_instance"] = self.ins_weight * bce

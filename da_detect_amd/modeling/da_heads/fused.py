@@ -80,7 +80,7 @@ class _DAInsHead(Function):
     `kinds`: ("bce",), ("cst",) or ("bce", "cst") — pass order = row order = order of the dropout draws."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, labels, means, masks1, masks2, grl, kinds, n_src):
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, labels, means, masks1, masks2, grl, kinds, n_src, row_end=None):
         R = x.shape[0]
         P = len(kinds)
         r_bce = R if "bce" in kinds else 0
@@ -93,9 +93,13 @@ class _DAInsHead(Function):
         h2.mul_(masks2.view(P * R, C2))
         w3v = w3.reshape(-1).contiguous()
         labels_f = labels.to(torch.float32) if r_bce else None
-        logits, sums = _C.da_ins_tail_forward(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, n_src)
+        if row_end is None:         # two images, [source, target]: the kernels that take n_src
+            logits, sums = _C.da_ins_tail_forward(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, n_src)
+        else:
+            row_end = tuple(row_end) if r_cst else (0,) * len(row_end)
+            logits, sums = _C.da_ins_tail_forward_n(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, row_end)
         ctx.save_for_backward(x, w1, w2, w3v, h1, h1s, masks1, h2, logits, labels_f, means if r_cst else None, grl)
-        ctx.conf = (R, P, r_bce, r_cst, n_src, tuple(w3.shape))
+        ctx.conf = (R, P, r_bce, r_cst, n_src, tuple(w3.shape), row_end)
         ctx.biases = (b1, b2)
         levels = int(means.shape[0]) if r_cst else 1
         bce = sums[0] / float(max(r_bce, 1))
@@ -108,15 +112,19 @@ class _DAInsHead(Function):
     @once_differentiable
     def backward(ctx, g_bce, g_cst, _g_logits):
         x, w1, w2, w3v, h1, h1s, masks1, h2, logits, labels_f, means, grl = ctx.saved_tensors
-        R, P, r_bce, r_cst, n_src, w3_shape = ctx.conf
+        R, P, r_bce, r_cst, n_src, w3_shape, row_end = ctx.conf
         need_x = ctx.needs_input_grad[0]
         C0, C1, C2 = x.shape[1], w1.shape[0], w2.shape[0]
         levels = int(means.shape[0]) if means is not None else 1
         coef = torch.stack([g_bce.reshape(()) / float(max(r_bce, 1)),
                             g_cst.reshape(()) / float(max(r_cst, 1) * levels)]).contiguous()
         # every mask value is 0 or 1 / keep, and a hidden unit that survived (h2 != 0) has mask 1 / keep
-        g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward(h2, w3v, logits, labels_f, means, coef, INS_DROPOUT_INV_KEEP,
-                                                            r_bce, r_cst, n_src)
+        if row_end is None:
+            g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward(h2, w3v, logits, labels_f, means, coef,
+                                                                INS_DROPOUT_INV_KEEP, r_bce, r_cst, n_src)
+        else:
+            g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward_n(h2, w3v, logits, labels_f, means, coef,
+                                                                  INS_DROPOUT_INV_KEEP, r_bce, r_cst, row_end)
         g_z2 = g_z2.view(P * R, C2, 1, 1)
         g_w2 = _C.conv_wgrad(h1s.view(P * R, C1, 1, 1), g_z2, (C2, C1, 1, 1), 1, 0).view(C2, C1)
         g_b2 = bias_grad(ctx.biases[1], g_z2)
@@ -128,25 +136,35 @@ class _DAInsHead(Function):
         g_x = None
         if need_x:
             g_x = _C.conv_forward(g1_x.view(R, C1, 1, 1), _C.conv_weight_transpose(w1.view(C1, C0, 1, 1))).view(R, C0)
-        return (g_x, g_w1, g_b1, g_w2, g_b2, g_w3.view(w3_shape), g_b3, None, g_means) + (None,) * 5
+        return (g_x, g_w1, g_b1, g_w2, g_b2, g_w3.view(w3_shape), g_b3, None, g_means) + (None,) * 6
 
 
 INS_DROPOUT_P = 0.5                                   # DAInsHead: F.dropout(p=0.5) after fc1 and fc2 (da_heads.py:63,65)
 INS_DROPOUT_INV_KEEP = 1.0 / (1.0 - INS_DROPOUT_P)
 
 
-def da_instance_head(x, head, labels, means, masks1, masks2, grl, kinds, n_src):
-    """x [R, C] ROI feature vectors; head a DAInsHead; labels [R] domain labels (1 = source); means [L, 2] per-level mean
-    sigmoid of the image head on (source, target) or None; masks1 / masks2 [P, R, 1024] dropout masks of the passes; grl
-    float [P] device tensor of the passes' gradient-reversal weights -> (mean BCE, consistency loss, logits [P, R])"""
+def da_instance_head(x, head, labels, means, masks1, masks2, grl, kinds, n_src, rows_per_image=None):
+    """x [R, C] ROI feature vectors; head a DAInsHead; labels [R] domain labels (1 = source); means [L, N] per-level mean
+    sigmoid of the image head on the N images or None; masks1 / masks2 [P, R, 1024] dropout masks of the passes; grl
+    float [P] device tensor of the passes' gradient-reversal weights; rows_per_image: host ints, how many of the R rows
+    (stacked in image order) belong to each image — without it N = 2 and the first n_src rows are the source image's
+    -> (mean BCE, consistency loss, logits [P, R])"""
+    row_end = None
+    if rows_per_image is not None:
+        rows_per_image = [int(r) for r in rows_per_image]
+        if sum(rows_per_image) != x.shape[0] or (means is not None and means.shape[1] != len(rows_per_image)):
+            raise ValueError("instance head: rows_per_image {} does not describe {} rows of {} images".format(
+                rows_per_image, x.shape[0], "?" if means is None else means.shape[1]))
+        if len(rows_per_image) != 2 or rows_per_image[0] != int(n_src):
+            row_end = tuple(sum(rows_per_image[:i + 1]) for i in range(len(rows_per_image)))
     return _DAInsHead.apply(x, head.fc1_da.weight, head.fc1_da.bias, head.fc2_da.weight, head.fc2_da.bias,
                             head.fc3_da.weight, head.fc3_da.bias, labels, means, masks1, masks2, grl, tuple(kinds),
-                            int(n_src))
+                            int(n_src), row_end)
 
 
 class _TripletW(Function):
-    """nn.TripletMarginLoss(margin, p=2) on [1,C,H,W] maps: distance over the LAST axis (W)
-    (reference: da_heads/loss.py:180-200)."""
+    """nn.TripletMarginLoss(margin, p=2) on [k,C,H,W] maps: distance over the LAST axis (W), mean over (k, C, H)
+    (reference: da_heads/loss.py:180-200, which passes k = 1)."""
 
     @staticmethod
     def forward(ctx, a, p, n, margin):
@@ -159,12 +177,14 @@ class _TripletW(Function):
     @once_differentiable
     def backward(ctx, g):
         a, p, n, dist = ctx.saved_tensors
-        _, C, H, W = a.shape
-        g_scale = (g / float(C * H)).reshape(1).contiguous()
+        k, C, H, W = a.shape
+        g_scale = (g / float(k * C * H)).reshape(1).contiguous()
         ga, gp, gn = _C.triplet_w_backward(a, p, n, dist, g_scale, ctx.margin, need=ctx.needs_input_grad[:3])
         return ga, gp, gn, None
 
 
 def triplet_margin_loss_w(anchor, positive, negative, margin):
-    assert anchor.dim() == 4 and anchor.shape[0] == 1, "image-level triplet loss expects [1,C,H,W] maps"
+    if anchor.dim() != 4 or anchor.shape[0] < 1 or anchor.shape != positive.shape or anchor.shape != negative.shape:
+        raise ValueError("image-level triplet loss expects three [k,C,H,W] maps of one shape, got {}, {}, {}".format(
+            tuple(anchor.shape), tuple(positive.shape), tuple(negative.shape)))
     return _TripletW.apply(anchor, positive, negative, float(margin))

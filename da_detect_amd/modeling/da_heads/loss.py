@@ -29,10 +29,11 @@ def da_ins_loss(da_ins, da_ins_labels):
     return F.binary_cross_entropy_with_logits(torch.squeeze(da_ins), da_ins_labels.to(torch.float32))
 
 
-def da_consist_loss(img_mean_sig, da_ins_consist, da_ins_labels):
-    """img_mean_sig: per-image mean sigmoid of one level, or a list with one entry per level"""
+def da_consist_loss(img_mean_sig, da_ins_consist, da_ins_labels, rows_per_image=None):
+    """img_mean_sig: per-image mean sigmoid of one level, or a list with one entry per level; rows_per_image: the instance
+    rows of each image (host ints) for batches of other than two images"""
     levels = img_mean_sig if isinstance(img_mean_sig, (list, tuple)) else [img_mean_sig]
-    return consistency_loss(levels, da_ins_consist, da_ins_labels, size_average=True)
+    return consistency_loss(levels, da_ins_consist, da_ins_labels, size_average=True, rows_per_image=rows_per_image)
 
 
 class TripletMargins(object):

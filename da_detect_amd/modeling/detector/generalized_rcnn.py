@@ -3,7 +3,8 @@
 
 forward(images, targets) -> dict of scalar losses (training) | list[BoxList] detections (eval).
 Batch layout contracts inherited from the reference trainer (engine/trainer.py:215-224): source images first;
-plain DA = [source, target]; triplet DA = [source, target(positive), auxiliary(negative)].
+plain DA = [source, target]; triplet DA = [source, target(positive), auxiliary(negative)].  This project's extension:
+k images per domain, [S_1..S_k, T_1..T_k(, A_1..A_k)] (elision.images_per_domain checks it); k = 1 is the reference's batch.
 """
 import os
 
@@ -14,7 +15,7 @@ from ...structures.image_list import to_image_list
 from ...utils.streams import record, side_stream
 from ..backbone import build_backbone
 from ..da_heads.da_heads import build_da_heads, build_da_heads_triplet
-from ..elision import elision_enabled, leading_source_images
+from ..elision import elision_enabled, images_per_domain, leading_source_images
 from ..roi_heads.roi_heads import build_roi_heads
 from ..rpn.rpn import build_rpn
 
@@ -36,14 +37,15 @@ class GeneralizedRCNN(nn.Module):
     def _images_with_read_proposals(self, targets):
         """number of leading images whose RPN proposals some loss reads: the source images always (detection losses);
         a target-domain image only through the instance-level features (or as the ROI set of the aligned triplet
-        passes); the auxiliary image of a triplet batch never (generalized_rcnn.py:100 passes proposals[0:2] on)"""
+        passes); the auxiliary images of a triplet batch never (generalized_rcnn.py:100 passes proposals[0:2] on; with k
+        images per domain that is proposals[0:2k])"""
         n_src = leading_source_images(targets)
         if n_src == 0:
             return None
         if self.da_heads_triplet:
-            if len(targets) != 3 or n_src != 1:
+            if len(targets) != 3 * n_src:
                 return None
-            return 2 if (self.da_heads_triplet.needs_instance_features or self.Aligned) else 1
+            return 2 * n_src if (self.da_heads_triplet.needs_instance_features or self.Aligned) else n_src
         return len(targets) if self.da_heads.needs_instance_features else n_src
 
     def forward(self, images, targets=None):
@@ -53,6 +55,9 @@ class GeneralizedRCNN(nn.Module):
         if self.training and images.tensors.is_cuda:
             # lets the RPN prepare its loss targets on a side stream without waiting for the backbone
             self.rpn.inputs_ready = torch.cuda.current_stream(images.tensors.device).record_event()
+        k = None
+        if self.training and (self.da_heads or self.da_heads_triplet):
+            k = images_per_domain(targets, 3 if self.da_heads_triplet else 2)
         features = self.backbone(images.tensors)
         holder = {}
         if self.training and self.da_heads and not self.da_heads_triplet and features[0].is_cuda:
@@ -94,17 +99,20 @@ class GeneralizedRCNN(nn.Module):
         if self.roi_heads:
             if self.training and self.da_heads_triplet:
                 f = features[0]
-                assert f.shape[0] == 3, "triplet training expects [source, target, auxiliary] batches"
-                da_img_fea_set = [[f[0:1]], [f[1:2]], [f[2:3]]]
-                ori_features, ori_targets = [f[0:2]], targets[0:2]
+                if f.shape[0] != 3 * k:
+                    raise ValueError("triplet training expects [source, target, auxiliary] batches: {} feature maps for "
+                                     "{} images per domain".format(f.shape[0], k))
+                da_img_fea_set = [[f[0:k]], [f[k:2 * k]], [f[2 * k:3 * k]]]
+                ori_features, ori_targets = [f[0:2 * k]], targets[0:2 * k]
                 self.roi_heads.box.ins_features_unused = not self.da_heads_triplet.needs_instance_features
                 x, result, detector_losses, da_ins_feas, da_ins_labels = self.roi_heads(
-                    ori_features, proposals[0:2], ori_targets)
+                    ori_features, proposals[0:2 * k], ori_targets)
                 if self.Aligned:
-                    # all three domains are pooled with the TARGET image's proposals (generalized_rcnn.py:110-112)
+                    # all three domains are pooled with the TARGET images' proposals (generalized_rcnn.py:110-112): row r of
+                    # the three sets is the same box on S_i, T_i and A_i (the pooler's batch index is the list position)
                     ins_set = []
-                    for fea, tgt in zip(da_img_fea_set, (targets[0], targets[1], targets[2])):
-                        _, _, _, feas, _ = self.roi_heads(fea, [proposals[1]], [tgt])
+                    for d, fea in enumerate(da_img_fea_set):
+                        _, _, _, feas, _ = self.roi_heads(fea, proposals[k:2 * k], targets[d * k:(d + 1) * k])
                         ins_set.append(feas)
                 else:
                     ins_set = [0, 0, 0]

@@ -30,3 +30,18 @@ def leading_source_images(targets):
     src = [is_source_image(t) for t in targets]
     n = sum(src)
     return n if all(src[:n]) else 0
+
+
+def images_per_domain(targets, domains):
+    """k of a training batch [S_1..S_k, T_1..T_k] (domains = 2) or [S_1..S_k, T_1..T_k, A_1..A_k] (domains = 3, triplet):
+    the source-domain images lead and every domain has as many images (engine/trainer.py:_da_batches builds it so).
+    Anything else raises ValueError — the heads slice the batch by k and would silently compare the wrong images."""
+    src = [bool(is_source_image(t)) for t in targets]
+    k = sum(src)
+    layout = "".join("S" if f else "-" for f in src)
+    if k == 0 or not all(src[:k]):
+        raise ValueError("DA batch: the source-domain images must come first, in one run; got %s (S = source)" % layout)
+    if len(targets) != domains * k:
+        raise ValueError("DA batch: %d domains of %d images each expected (as many as source images), got %d images: %s"
+                         % (domains, k, len(targets), layout))
+    return k

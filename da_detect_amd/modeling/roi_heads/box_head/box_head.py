@@ -141,6 +141,9 @@ class ROIBoxHead(torch.nn.Module):
         # number of source-domain rows, known on the host: spares consistency_loss its nonzero() round trip
         da_ins_labels._n_src_host = sum(len(p) for p, t in zip(self.loss_evaluator._proposals, targets)
                                         if is_source_image(t))
+        # rows of each image, in image order (the rows are stacked that way): the consistency term compares every ROI with
+        # the mean of its own image
+        da_ins_labels._rows_per_image_host = tuple(len(p) for p in self.loss_evaluator._proposals)
         return (x, proposals, dict(loss_classifier=loss_classifier, loss_box_reg=loss_box_reg), da_ins_feas,
                 da_ins_labels)
 

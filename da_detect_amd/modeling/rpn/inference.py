@@ -41,6 +41,10 @@ _ROWS_TOPK = True
 # False: multi-level training selection with the reference's host round trips (the path taken on CPU tensors and in eval
 # mode; tests/test_model_gpu.py compares the two)
 _DEVICE_SELECT = True
+# a level with at least this many images on the device: ONE batched NMS call for all of them (dadet_nms_batch: the images'
+# one-workgroup sweeps run side by side) instead of per-image chains alternating over two streams; fewer images keep the
+# per-image chains.  Same kept positions and counts (tests/test_nms_batch_gpu.py); tools/nms_time.py --batch N times both
+_NMS_BATCH_MIN = 4
 # (measured in round 3 and removed: the device-side selection as one captured HIP graph — 64.5 - 65.5 ms per step against
 # 59.4 - 60.8 launch by launch; replaying the ~250-node graph cost more than issuing its launches from Python)
 
@@ -119,6 +123,15 @@ class RPNPostProcessor(torch.nn.Module):
             main, side = torch.cuda.current_stream(dev), other_stream(dev)
             side.wait_stream(main)      # sorted scores / deltas exist
         pending = []
+        # (every image of a level hands the same number of ranked boxes over when no small-box filter runs)
+        n_rank = pre_nms_top_n if prepared is None else int(topk_idx[0].shape[0])
+        batched = (use_side and N >= _NMS_BATCH_MIN and n_rank <= _C.NMS_BATCH_MAX_BOXES and N <= _C.NMS_BATCH_MAX_IMAGES
+                   and (topk_idx is None or all(int(t.shape[0]) == n_rank for t in topk_idx)))
+        boxes_all = None
+        if batched:
+            boxes_all = torch.empty((N, n_rank, 4), dtype=torch.float32, device=dev)
+            if not torch.cuda.is_current_stream_capturing():
+                boxes_all.record_stream(side)     # every second image's decode writes its rows there
         for i in range(N):
             im_w, im_h = anchors[i].size
             ctx = torch.cuda.stream(side) if (use_side and i % 2 == 1) else contextlib.nullcontext()
@@ -129,13 +142,14 @@ class RPNPostProcessor(torch.nn.Module):
                 else:
                     scores, idx_i = sorted_scores[i], topk_idx[i]
                 boxes = _C.rpn_decode_clip(deltas_all[i], anchors[i].bbox.contiguous(), idx_i,
-                                           self.box_coder.weights, self.box_coder.bbox_xform_clip, im_w, im_h)
+                                           self.box_coder.weights, self.box_coder.bbox_xform_clip, im_w, im_h,
+                                           out=boxes_all[i] if batched else None)
                 if self.min_size > 0:  # with min_size == 0 every clipped box passes (w, h >= 1)
                     keep = ((boxes[:, 2] - boxes[:, 0] + 1 >= self.min_size) &
                             (boxes[:, 3] - boxes[:, 1] + 1 >= self.min_size)).nonzero().squeeze(1)
                     boxes, scores = boxes[keep].contiguous(), scores[keep].contiguous()
                 keep = count = None
-                if self.nms_thresh > 0:
+                if self.nms_thresh > 0 and not batched:
                     # boxes arrive in the order of the stable descending score sort above: NMS needs no ranking pass
                     # (a min_size filter keeps the relative order too)
                     keep, count = _C.nms_with_count(boxes, None, self.nms_thresh, max_keep=self.post_nms_top_n)
@@ -144,6 +158,11 @@ class RPNPostProcessor(torch.nn.Module):
             if not torch.cuda.is_current_stream_capturing():     # (a captured graph owns its memory: nothing to register)
                 record([p[:4] for p in pending[1::2]], main)
             main.wait_stream(side)
+        if batched:
+            keep_all, count_all = _C.nms_batch_with_count(boxes_all, [n_rank] * N, self.nms_thresh,
+                                                          max_keep=self.post_nms_top_n)
+            pending = [(boxes, scores, keep_all[i], count_all[i:i + 1], size)
+                       for i, (boxes, scores, _, _, size) in enumerate(pending)]
         if raw:
             return pending
         if self.defer and self.training and self.nms_thresh > 0 and self.min_size <= 0 and dev.type == "cuda":

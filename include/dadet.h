@@ -63,6 +63,16 @@ int dadet_nms_workspace_bytes(int n, size_t* bytes_out);
 int dadet_nms(const float* boxes_xyxy, const float* scores, int n, float thresh, int tie_rule,
               int max_keep, void* workspace, size_t workspace_bytes, int64_t* keep_out,
               int* num_keep_out, void* stream);
+/* A batch of up to 64 PRE-RANKED images in one launch per stage (IoU tiles, 256-box block sweep, compaction), the image taken
+ * from a grid dimension: independent images are independent workgroups, so their sweeps overlap.  boxes_xyxy
+ * [batch][n_max][4] (best first; image i uses its first n_host[i] <= n_max <= 16384 boxes), n_host a HOST array (copied into
+ * the launch arguments), keep_out int64 [batch][n_max], num_keep_out int32 [batch] (device).  Image i's kept positions and
+ * count are exactly those of dadet_nms(boxes_i, NULL, n_host[i], ...) — the same device code on the same arguments; an
+ * image with n_host[i] == 0 gets count 0.  workspace: batch slices of dadet_nms_workspace_bytes(n_max). */
+int dadet_nms_batch_workspace_bytes(int batch, int n_max, size_t* bytes_out);
+int dadet_nms_batch(const float* boxes_xyxy, const int* n_host, int batch, int n_max, float thresh, int tie_rule,
+                    int max_keep, void* workspace, size_t workspace_bytes, int64_t* keep_out, int* num_keep_out,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ROIAlign — replaces `_C.roi_align_forward` / `_C.roi_align_backward`
@@ -692,6 +702,19 @@ int dadet_da_ins_tail_backward(const float* h, const float* w3, const float* log
                                const float* means, const float* coef, float inv_keep, float* g_z, float* g_w3,
                                float* g_b3, float* g_means, int R_bce, int R_cst, int n_src, int levels, int C,
                                void* stream);
+/* The same tail for num_images images (1..64).  The consistency rows are stacked image by image; row_end[num_images] (HOST
+ * array, copied into the launch's arguments: no device buffer, no synchronisation) holds the ascending ends of the images'
+ * row segments, row_end[num_images - 1] == R_cst; an image may own no row.  means / g_means are [levels][num_images], and
+ * consistency row j of image i adds sum_l |means[l][i] - sigmoid(logit_j)|.  The backward keeps levels * num_images <= 512
+ * sums in LDS.  Bad arguments are refused before anything is written.  num_images = 2 with row_end = {n_src, R_cst} gives the
+ * forward bits of dadet_da_ins_tail_forward. */
+int dadet_da_ins_tail_forward_n(const float* h, const float* w3, const float* b3, const float* labels,
+                                const float* means, float* logits, float* sums, int R_bce, int R_cst,
+                                const int* row_end, int num_images, int levels, int C, void* stream);
+int dadet_da_ins_tail_backward_n(const float* h, const float* w3, const float* logits, const float* labels,
+                                 const float* means, const float* coef, float inv_keep, float* g_z, float* g_w3,
+                                 float* g_b3, float* g_means, int R_bce, int R_cst, const int* row_end, int num_images,
+                                 int levels, int C, void* stream);
 int dadet_da_ins_dropout_rows(const float* h1, const float* masks, float* out, int64_t numel_per_pass, int passes,
                               void* stream);
 int dadet_da_ins_merge(const float* g, const float* masks, const float* h1, const float* grl, float* g_w, float* g_x,

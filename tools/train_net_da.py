@@ -119,8 +119,11 @@ def main():
                 bench.benchmark_init(model, 100)
         model.train()
         enable_overlapped_rpn_backward(model)
-        n_img = 3 if cfg.MODEL.DA_HEADS.TRIPLET_USE else 2
-        images, targets = make_batch(cfg, n_img, 608, 1216, seed=100 + get_rank(), device=device)
+        # k images per domain, as the data loaders would give them (data/build.py:images_per_gpu): [S_1..S_k, T_1..T_k(,
+        # A_1..A_k)]; at least the reference's one per domain
+        k = max(1, cfg.SOLVER.IMS_PER_BATCH // (2 * world)) if cfg.MODEL.DOMAIN_ADAPTATION_ON else 1
+        n_img = (3 if cfg.MODEL.DA_HEADS.TRIPLET_USE else 2) * k
+        images, targets = make_batch(cfg, n_img, 608, 1216, seed=100 + get_rank(), device=device, num_source=k)
         for it in range(args.synthetic):
             losses = train_step(model, optimizer, images, targets, scheduler, it)
             if it % 5 == 0 or it == args.synthetic - 1:

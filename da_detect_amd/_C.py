@@ -211,6 +211,44 @@ def nms_batch_with_count(boxes, counts, threshold, max_keep=-1, tie_rule=None, w
     return keep, count
 
 
+DETECT_POST_MAX_IMAGES = 64      # per call: the by-value table of per-image row counts (csrc/detect_post.hip)
+DETECT_POST_READ_COUNTS = 0      # 1: one host read of the candidate counts, sweep over candidates only (A/B)
+
+
+def detect_post(boxes, scores, rows, score_thresh, nms_thresh, detections_per_img, tie_rule=None, read_counts=None):
+    """PostProcessor.filter_results for a batch in one fixed sequence of launches (dadet_detect_post): boxes [sum(rows), C, 4]
+    decoded and clipped, scores [sum(rows), C], rows host ints per image (at most DETECT_POST_MAX_IMAGES images of at most
+    NMS_BATCH_MAX_BOXES rows) -> list of (boxes [n, 4], scores [n], labels int64 [n]) per image, in the reference's order.
+    One host wait (the final counts); two with read_counts."""
+    _dev(boxes, "boxes")
+    _dev(scores, "scores")
+    rows = [int(r) for r in rows]
+    B, C = len(rows), int(scores.shape[1])
+    total = sum(rows)
+    assert scores.shape[0] == total and boxes.numel() == total * C * 4
+    boxes, scores = boxes.contiguous(), scores.contiguous()
+    cap = total * (C - 1)
+    out_boxes = torch.empty((cap, 4), dtype=torch.float32, device=boxes.device)
+    out_scores = torch.empty(cap, dtype=torch.float32, device=boxes.device)
+    out_labels = torch.empty(cap, dtype=torch.int64, device=boxes.device)
+    counts = torch.empty(max(B, 1), dtype=torch.int32, device=boxes.device)
+    rows_host = (ctypes.c_int * max(B, 1))(*rows)
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_detect_post_workspace_bytes", rows_host, B, C, ctypes.byref(nbytes))
+    ws = _workspace(nbytes.value, boxes.device)
+    rule = NMS_TIE_RULE if tie_rule is None else tie_rule
+    mode = DETECT_POST_READ_COUNTS if read_counts is None else read_counts
+    _lib.call("dadet_detect_post", _p(boxes), _p(scores), rows_host, B, C, float(score_thresh), float(nms_thresh), int(rule),
+              int(detections_per_img), int(mode), _p(ws), ctypes.c_size_t(ws.numel()), _p(out_boxes), _p(out_scores),
+              _p(out_labels), _p(counts), _stream())
+    n_out = counts.tolist() if B else []
+    results, at = [], 0
+    for r, n in zip(rows, n_out):
+        results.append((out_boxes[at:at + n], out_scores[at:at + n], out_labels[at:at + n]))
+        at += r * (C - 1)
+    return results
+
+
 def nms(dets, scores, threshold):
     """_C.nms(dets[N,4], scores[N], thr) -> int64[K] kept original indices, ascending (nms.h:10-28)."""
     if dets.numel() == 0:

@@ -79,6 +79,9 @@ _SIGNATURES = {
     "dadet_nms": [_P, _P, c_int, c_float, c_int, c_int, _P, c_size_t, _P, _P, _P],
     "dadet_nms_batch_workspace_bytes": [c_int, c_int, POINTER(c_size_t)],
     "dadet_nms_batch": [_P, POINTER(c_int), c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P, _P, _P],
+    "dadet_detect_post_workspace_bytes": [POINTER(c_int), c_int, c_int, POINTER(c_size_t)],
+    "dadet_detect_post": [_P, _P, POINTER(c_int), c_int, c_int, c_float, c_float, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P,
+                          _P, _P],
     "dadet_roi_align_forward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],

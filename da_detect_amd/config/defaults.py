@@ -84,7 +84,10 @@ _DEFAULTS = {
         "WARMUP_METHOD": "linear", "WARMUP_LR": 0.0001, "LR_MIN": 0.000001, "CHECKPOINT_PERIOD": 2500,
         "IMS_PER_BATCH": 16,
     },
-    "TEST": {"EXPECTED_RESULTS": [], "EXPECTED_RESULTS_SIGMA_TOL": 4, "IMS_PER_BATCH": 8, "DETECTIONS_PER_IMG": 100},
+    "TEST": {"EXPECTED_RESULTS": [], "EXPECTED_RESULTS_SIGMA_TOL": 4, "IMS_PER_BATCH": 8, "DETECTIONS_PER_IMG": 100,
+             # test-time box augmentation (reference defaults.py:410-425, engine/bbox_aug.py): extra passes over the flipped
+             # image and over SCALES (shorter side, longer side capped at MAX_SIZE), merged and filtered once
+             "BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False}},
     "TENSORBOARD_EXPERIMENT": "logs/maskrcnn-benchmark",
     "PATHS_CATALOG": os.path.join(os.path.dirname(__file__), "paths_catalog.py"),
 }

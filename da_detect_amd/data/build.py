@@ -18,7 +18,7 @@ from ..utils.comm import get_world_size
 from ..utils.imports import load_paths_catalog
 from . import datasets as D
 from . import samplers
-from .collate_batch import BatchCollator, BatchCollator_triplet
+from .collate_batch import BatchCollator, BatchCollator_triplet, BBoxAugCollator
 from .datasets import COCODataset, TripletDataset
 from .transforms import build_transforms
 
@@ -143,9 +143,12 @@ def make_data_loader(cfg, is_train=True, is_source=True, is_negative=False, is_d
         names = cfg.DATASETS.SOURCE_TRAIN
     else:
         names = cfg.DATASETS.TARGET_TRAIN_negative if is_negative else cfg.DATASETS.TARGET_TRAIN
-    datasets = build_dataset(list(names), build_transforms(cfg, is_train), _catalog(cfg), is_train, is_source)
-    loaders = [_loader_for(cfg, ds, per_gpu, shuffle, is_distributed, num_iters, start_iter,
-                           BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)) for ds in datasets]
+    # evaluation with test-time augmentation: untransformed images, unbatched (build.py:155,168)
+    aug = (not is_train) and cfg.TEST.BBOX_AUG.ENABLED
+    transforms = None if aug else build_transforms(cfg, is_train)
+    collator = BBoxAugCollator() if aug else BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
+    datasets = build_dataset(list(names), transforms, _catalog(cfg), is_train, is_source)
+    loaders = [_loader_for(cfg, ds, per_gpu, shuffle, is_distributed, num_iters, start_iter, collator) for ds in datasets]
     if is_train:
         assert len(loaders) == 1
         return loaders[0]
@@ -179,9 +182,14 @@ def _train_loader(cfg, dataset, is_distributed, start_iter, collator):
 
 
 def make_test_data_loader(cfg, dataset, is_distributed=False):
-    """evaluation loader over an already constructed dataset (sequential, or sharded by rank when distributed)"""
-    return _loader_for(cfg, dataset, images_per_gpu(cfg, False), bool(is_distributed), is_distributed, None, 0,
-                       BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY))
+    """evaluation loader over an already constructed dataset (sequential, or sharded by rank when distributed).  With
+    cfg.TEST.BBOX_AUG.ENABLED the samples leave it untransformed and unbatched (transforms=None and BBoxAugCollator,
+    build.py:155,168): the dataset's transforms are taken off here, the augmentation passes apply their own."""
+    collator = BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
+    if cfg.TEST.BBOX_AUG.ENABLED:
+        dataset._transforms = None
+        collator = BBoxAugCollator()
+    return _loader_for(cfg, dataset, images_per_gpu(cfg, False), bool(is_distributed), is_distributed, None, 0, collator)
 
 
 def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0):

@@ -25,6 +25,14 @@ class BatchCollator_triplet(object):
                 to_image_list(t[4], self.size_divisible), t[5], t[6], t[7], t[8])
 
 
+class BBoxAugCollator(object):
+    """for test-time augmentation (collate_batch.py:58-68): images, targets and ids pass through as tuples, unbatched —
+    every augmentation pass builds its own ImageList from the untransformed images"""
+
+    def __call__(self, batch):
+        return list(zip(*batch))
+
+
 class RawBatchCollator(object):
     """for the device-side pipeline: keeps decoded uint8 images and untransformed targets as lists"""
 

@@ -13,19 +13,30 @@ import time
 
 import torch
 
+from ..data.collate_batch import BBoxAugCollator
+from .bbox_aug import im_detect_bbox_aug
 from ..utils.comm import all_gather, get_world_size, is_main_process, synchronize
 
 
-def compute_on_dataset(model, data_loader, device):
-    """engine/inference.py:18-52: batches are (images, targets, image_ids) -> {image_id: BoxList on CPU}"""
+def compute_on_dataset(model, data_loader, device, bbox_aug=False, timer=None):
+    """engine/inference.py:18-52: batches are (images, targets, image_ids) -> {image_id: BoxList on CPU}.  With
+    `bbox_aug` the batches are the untransformed images of BBoxAugCollator and go through the augmentation passes;
+    `timer` (tic() / toc()), when given, brackets the model time as in the reference."""
     model.eval()
     results = {}
     cpu = torch.device("cpu")
     for batch in data_loader:
         images, _, image_ids = batch
-        images = images.to(device)
         with torch.no_grad():
-            output = model(images)
+            if timer:
+                timer.tic()
+            if bbox_aug:
+                output = im_detect_bbox_aug(model, images, device)
+            else:
+                output = model(images.to(device))
+            if timer:
+                torch.cuda.synchronize()
+                timer.toc()
         results.update({i: o.to(cpu) for i, o in zip(image_ids, output)})
     return results
 
@@ -64,16 +75,21 @@ def prepare_for_coco_detection(predictions, dataset):
 
 
 def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=False, device="cuda",
-              expected_results=(), expected_results_sigma_tol=4, output_folder=None, evaluate=None):
+              expected_results=(), expected_results_sigma_tol=4, output_folder=None, evaluate=None,
+              bbox_aug=False):
     """engine/inference.py:76-129.  `evaluate(dataset, predictions, output_folder, **extra)` is the dataset-specific
-    scorer (pycocotools in the reference); when None the bbox records are written / returned instead."""
+    scorer (pycocotools in the reference); when None the bbox records are written / returned instead.
+    A loader built with cfg.TEST.BBOX_AUG.ENABLED (data/build.py) hands out untransformed, unbatched images, which only the
+    augmentation passes can take: its BBoxAugCollator selects them like `bbox_aug=True`, so a caller that builds model and
+    loader from one configuration (tools/test_net_da.py) needs no argument of its own."""
+    bbox_aug = bool(bbox_aug) or isinstance(getattr(data_loader, "collate_fn", None), BBoxAugCollator)
     device = torch.device(device)
     num_devices = get_world_size()
     logger = logging.getLogger("maskrcnn_benchmark.inference")
     dataset = data_loader.dataset
     logger.info("Start evaluation on %s dataset(%d images).", dataset_name, len(dataset))
     start = time.time()
-    predictions = compute_on_dataset(model, data_loader, device)
+    predictions = compute_on_dataset(model, data_loader, device, bbox_aug)
     synchronize()
     total = time.time() - start
     logger.info("Total inference time: %s (%s s / img per device, on %d devices)",

@@ -26,6 +26,7 @@ _DA_AFTER_RPN = True
 class GeneralizedRCNN(nn.Module):
     def __init__(self, cfg):
         super(GeneralizedRCNN, self).__init__()
+        self.cfg = cfg          # read by the test-time augmentation passes (engine/bbox_aug.py)
         self.backbone = build_backbone(cfg)
         self.rpn = build_rpn(cfg)
         self.roi_heads = build_roi_heads(cfg)

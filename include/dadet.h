@@ -75,6 +75,28 @@ int dadet_nms_batch(const float* boxes_xyxy, const int* n_host, int batch, int n
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Detection filter — replaces `PostProcessor.filter_results` for a whole batch
+ *   reference: modeling/roi_heads/box_head/inference.py:108-149 (per image and class: nonzero, gathers, _C.nms, full;
+ *   then kthvalue on the host), structures/boxlist_ops.py:11-34.
+ * boxes [sum R_i][C][4] decoded and clipped, scores [sum R_i][C] softmax (fp32, row-major, image after image);
+ * rows_host[batch] the R_i (HOST, batch <= 64, R_i <= 16384).  Per image, in the reference's order (class ascending, row
+ * ascending inside a class): candidates of class j >= 1 are the rows with score > score_thresh (strict), greedy "+1" NMS per
+ * class with tie_rule as in dadet_nms (ranked by score descending, row ascending), nms_thresh <= 0 = no suppression; if
+ * n > detections_per_img > 0 every detection with score >= the detections_per_img-th largest score stays (ties at the cut
+ * give more).  Image i's detections are written from row (sum of R_k, k < i) * (C - 1) of out_boxes [.][4], out_scores and
+ * out_labels (int64), capacity sum R_i * (C - 1) rows each; out_counts int32 [batch] (device).
+ * A fixed sequence of launches, independent of C: rank (one workgroup per image and class, LDS sort), dadet_nms_batch in
+ * chunks of at most 64 ranked sets, emit.  read_counts 0: the sweep runs over all R_i ranked rows and nothing waits on the
+ * host; 1: ONE blocking read of the per-(image, class) candidate counts lets it run over the candidates only — the single
+ * exception to "nothing synchronises" above.  Same result either way, bit for bit; no float atomics.
+ * ----------------------------------------------------------------------------------------------*/
+int dadet_detect_post_workspace_bytes(const int* rows_host, int batch, int num_classes, size_t* bytes_out);
+int dadet_detect_post(const float* boxes, const float* scores, const int* rows_host, int batch, int num_classes,
+                      float score_thresh, float nms_thresh, int tie_rule, int detections_per_img, int read_counts,
+                      void* workspace, size_t workspace_bytes, float* out_boxes, float* out_scores, int64_t* out_labels,
+                      int* out_counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ROIAlign — replaces `_C.roi_align_forward` / `_C.roi_align_backward`
  *   reference: csrc/ROIAlign.h:11-45, csrc/cpu/ROIAlign_cpu.cpp:114-257, csrc/cuda/ROIAlign_cuda.cu:65-254.
  * input  [B][H][W][C] NHWC, rois [R][5] = (batch_idx, x1, y1, x2, y2), output [R][PH][PW][C] NHWC.

@@ -249,6 +249,67 @@ def detect_post(boxes, scores, rows, score_thresh, nms_thresh, detections_per_im
     return results
 
 
+COCO_MATCH_MAX_DETS = 100        # detections per (image, category) pair after the cut (csrc/coco_match.hip)
+
+
+def _int_table(values):
+    values = [int(v) for v in values]
+    return (ctypes.c_int * max(len(values), 1))(*values), len(values)
+
+
+def _f64_table(values):
+    values = [float(v) for v in values]
+    return (ctypes.c_double * max(len(values), 1))(*values), len(values)
+
+
+def coco_match_workspace_bytes(det_off, gt_off, n_det, n_gt, n_thr, n_area):
+    """scratch of coco_match for these offset tables; validates them on the host exactly as the launch does (no device)"""
+    d_host, nd = _int_table(det_off)
+    g_host, ng = _int_table(gt_off)
+    if nd != ng or nd < 1:
+        raise _lib.DadetError("coco_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_coco_match_workspace_bytes", d_host, g_host, nd - 1, int(n_det), int(n_gt), int(n_thr), int(n_area),
+              ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def coco_match(det_box, gt_box, gt_area, gt_crowd, det_off, gt_off, iou_thr, area_rng):
+    """COCO box matching of every (image, category) pair in one launch (dadet_coco_match): det_box [Nd, 4] / gt_box [Ng, 4]
+    xywh float64, gt_area [Ng] float64, gt_crowd [Ng] int32 on the device; det_off / gt_off host ints [P + 1] (pair p's slices;
+    detections best first, at most COCO_MATCH_MAX_DETS); iou_thr [T] and area_rng [A][2] host floats ->
+    (matched uint8 [T, A, Nd], ignored uint8 [T, A, Nd], npig int32 [P, A]) on the device."""
+    for t, name, dtype in ((det_box, "det_box", torch.float64), (gt_box, "gt_box", torch.float64),
+                           (gt_area, "gt_area", torch.float64), (gt_crowd, "gt_crowd", torch.int32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.DadetError(
+                "%s must be a tensor on the HIP device: the da_detect_amd operators have no CPU path" % name)
+        if t.dtype != dtype:
+            raise _lib.DadetError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    det_box, gt_box, gt_area, gt_crowd = det_box.contiguous(), gt_box.contiguous(), gt_area.contiguous(), gt_crowd.contiguous()
+    n_det, n_gt = int(det_box.shape[0]), int(gt_box.shape[0])
+    if det_box.numel() != 4 * n_det or gt_box.numel() != 4 * n_gt or gt_area.numel() != n_gt or gt_crowd.numel() != n_gt:
+        raise _lib.DadetError("coco_match: boxes must be [n, 4], gt_area and gt_crowd [n_gt]")
+    d_host, nd = _int_table(det_off)
+    g_host, ng = _int_table(gt_off)
+    if nd != ng or nd < 1:
+        raise _lib.DadetError("coco_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
+    pairs = nd - 1
+    thr_host, T = _f64_table(iou_thr)
+    rng_host, A2 = _f64_table([v for lo_hi in area_rng for v in lo_hi])
+    A = A2 // 2
+    dev = det_box.device
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_coco_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T, A, ctypes.byref(nbytes))
+    ws = _workspace(nbytes.value, dev)
+    matched = torch.empty((T, A, n_det), dtype=torch.uint8, device=dev)
+    ignored = torch.empty((T, A, n_det), dtype=torch.uint8, device=dev)
+    npig = torch.empty((pairs, A), dtype=torch.int32, device=dev)
+    _lib.call("dadet_coco_match", _p(det_box), _p(gt_box), _p(gt_area), _p(gt_crowd), d_host, g_host, pairs, n_det, n_gt,
+              thr_host, T, rng_host, A, _p(ws), ctypes.c_size_t(ws.numel()), _p(matched), _p(ignored), _p(npig), _stream())
+    return matched, ignored, npig
+
+
 def nms(dets, scores, threshold):
     """_C.nms(dets[N,4], scores[N], thr) -> int64[K] kept original indices, ascending (nms.h:10-28)."""
     if dets.numel() == 0:

@@ -30,6 +30,13 @@ _SUBMODULES = [
     "utils.imports", "utils.env", "utils.logger", "utils.miscellaneous", "utils.metric_logger", "utils.collect_env",
     "config.paths_catalog", "engine.trainer", "parallel", "parallel.reducer",
 ]
+# the reference keeps its scorers in a sub-package of `data.datasets`; here `data/datasets.py` is a module and the scorers are
+# `data.evaluation` (reference path below `maskrcnn_benchmark.` -> this package's path below `da_detect_amd.`)
+_RELOCATED = {
+    "data.datasets.evaluation": "data.evaluation",
+    "data.datasets.evaluation.coco": "data.evaluation.coco",
+    "data.datasets.evaluation.coco.coco_eval": "data.evaluation.coco.coco_eval",
+}
 
 
 def _alias_timm():
@@ -56,5 +63,9 @@ def install(prefix="maskrcnn_benchmark"):
     for sub in _SUBMODULES:
         mod = importlib.import_module("da_detect_amd." + sub)
         sys.modules[prefix + "." + sub] = mod
+    for theirs, ours in _RELOCATED.items():
+        sys.modules[prefix + "." + theirs] = importlib.import_module("da_detect_amd." + ours)
+    # `import maskrcnn_benchmark.data.datasets.evaluation as e` walks attributes: the module needs the name
+    importlib.import_module("da_detect_amd.data.datasets").evaluation = sys.modules[prefix + ".data.datasets.evaluation"]
     _alias_timm()
     return root

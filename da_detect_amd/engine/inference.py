@@ -1,10 +1,11 @@
 """Evaluation loop and the detection-record boundary (reference: maskrcnn_benchmark/engine/inference.py:18-129,
 data/datasets/evaluation/coco/coco_eval.py:81-112).
 
-The model's eval forward runs on the HIP kernels; everything after it is host-side bookkeeping.  COCO mAP itself is
-pycocotools arithmetic (parity unpinned, third party) — this module stops at the `bbox.json` records,
-which is the boundary the reference hands to pycocotools.  A dataset only needs `id_to_img_map`, `get_img_info(i)`
-and `contiguous_category_id_to_json_id` (the three members prepare_for_coco_detection touches)."""
+The model's eval forward runs on the HIP kernels; what follows is host-side bookkeeping up to the `bbox.json` records,
+the boundary the reference hands to pycocotools.  Scoring them is `data.evaluation.evaluate` (box AP matched on the device,
+proposal recall on the host), passed in as `evaluate`; without it this module stops at the records.  For the
+records a dataset only needs `id_to_img_map`, `get_img_info(i)` and `contiguous_category_id_to_json_id` (the three members
+prepare_for_coco_detection touches)."""
 import datetime
 import json
 import logging
@@ -78,7 +79,9 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
               expected_results=(), expected_results_sigma_tol=4, output_folder=None, evaluate=None,
               bbox_aug=False):
     """engine/inference.py:76-129.  `evaluate(dataset, predictions, output_folder, **extra)` is the dataset-specific
-    scorer (pycocotools in the reference); when None the bbox records are written / returned instead.
+    scorer (`data.evaluation.evaluate`; pycocotools in the reference) and its result is returned; when None the bbox
+    records are written / returned instead — except for `box_only` proposals without a `scores` field, from which no records
+    can be built: those go to the package's scorer for their recalls.
     A loader built with cfg.TEST.BBOX_AUG.ENABLED (data/build.py) hands out untransformed, unbatched images, which only the
     augmentation passes can take: its BBoxAugCollator selects them like `bbox_aug=True`, so a caller that builds model and
     loader from one configuration (tools/test_net_da.py) needs no argument of its own."""
@@ -99,6 +102,10 @@ def inference(model, data_loader, dataset_name, iou_types=("bbox",), box_only=Fa
         return None
     if output_folder:
         torch.save(predictions, os.path.join(output_folder, "predictions.pth"))
+    if evaluate is None and box_only and any(len(p) and not p.has_field("scores") for p in predictions):
+        # proposals of an RPN-only model: they carry `objectness`, not `scores`, so there are no detection records to
+        # build (this used to end in a KeyError); what can be computed from them is the proposal recall
+        from ..data.evaluation import evaluate
     if evaluate is not None:
         return evaluate(dataset=dataset, predictions=predictions, output_folder=output_folder, box_only=box_only,
                         iou_types=iou_types, expected_results=expected_results,

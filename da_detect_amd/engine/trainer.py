@@ -302,6 +302,7 @@ def do_da_train(model, source_data_loader, positive_target_data_loader, negative
     `checkpoint_period` iterations except at 0, `model_final` at max_iter - 1, periodic evaluation on
     `data_loader_val[0]` when cfg.MODEL.EVAL_USE_IN_TRAINING.  NaN losses end the run (tested at the logging period
     and at every checkpoint instead of every iteration: the test is a host synchronisation)."""
+    from ..data.evaluation import evaluate
     from .inference import inference
 
     logger = logging.getLogger("maskrcnn_benchmark.trainer")
@@ -353,7 +354,8 @@ def do_da_train(model, source_data_loader, positive_target_data_loader, negative
                 inference(net, data_loader_val[0], dataset_name="[Validation]", iou_types=("bbox",),
                           box_only=False if cfg.MODEL.RETINANET_ON else cfg.MODEL.RPN_ONLY, device=cfg.MODEL.DEVICE,
                           expected_results=cfg.TEST.EXPECTED_RESULTS,
-                          expected_results_sigma_tol=cfg.TEST.EXPECTED_RESULTS_SIGMA_TOL, output_folder=None)
+                          expected_results_sigma_tol=cfg.TEST.EXPECTED_RESULTS_SIGMA_TOL, output_folder=None,
+                          evaluate=evaluate)      # logs AP, AP50 ... and the per-category values (main process only)
             synchronize()
             net.train()
     tuner.close()

@@ -97,6 +97,34 @@ int dadet_detect_post(const float* boxes, const float* scores, const int* rows_h
                       int* out_counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * COCO box matching — the per-(image, category) matching of COCO's bbox evaluation for a whole dataset in ONE launch
+ *   (the reference leaves it to pycocotools: data/datasets/evaluation/coco/coco_eval.py:316-336).
+ * Pair p holds detections det_off_host[p] .. det_off_host[p+1] (at most 100, already in descending score) and ground truths
+ * gt_off_host[p] .. gt_off_host[p+1] (annotation order, any number).  det_box [n_det][4] and gt_box [n_gt][4] are xywh float64,
+ * gt_area [n_gt] float64 (the annotation's `area`), gt_crowd [n_gt] int32.  iou_thr_host [n_thr <= 16] and area_rng_host
+ * [n_area <= 4][2] = (lo, hi) are HOST arrays passed by value; n_thr * n_area <= 64.
+ * One workgroup per pair: IoU = i / ((da + ga) - i) with i = max(w, 0) * max(h, 0), w = min(dx + dw, gx + gw) - max(dx, gx)
+ * (no "+1"), i / da for a crowd ground truth, 0 for an empty intersection — float64, contraction off, so bit-identical to a
+ * host evaluation of the same expressions.  Then per (threshold t, area range a), detections in order: a ground truth is
+ * ignored if crowd or area < lo or area > hi; best = min(t, 1 - 1e-10); the non-ignored ground truths in order, then (only
+ * while nothing is matched) the ignored ones; one already taken at this (t, a) is skipped unless crowd; iou < best is
+ * skipped, otherwise it becomes the match and best its IoU; a matched detection inherits its match's ignored flag, an
+ * unmatched one is ignored if w * h of its own box is outside [lo, hi]; a matched non-crowd ground truth is taken.
+ * Outputs (device): matched_out, ignored_out uint8 [n_thr][n_area][n_det]; npig_out int32 [pairs][n_area] = non-ignored
+ * ground truths of the pair.  The offset tables are validated on the host (start at 0, never decrease, end at n_det / n_gt,
+ * at most 100 detections per pair) BEFORE anything is launched — DADET_EINVAL otherwise — and the validated copy is what the
+ * kernel reads: the call uploads it into the workspace and waits for that upload (its one host wait).  The matrix of a pair
+ * lives in LDS when it fits 160 KiB, else in the workspace; the query sizes it.  No atomics; nothing depends on timing.
+ * ----------------------------------------------------------------------------------------------*/
+int dadet_coco_match_workspace_bytes(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt, int n_thr,
+                                     int n_area, size_t* bytes_out);
+int dadet_coco_match(const double* det_box, const double* gt_box, const double* gt_area, const int* gt_crowd,
+                     const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt,
+                     const double* iou_thr_host, int n_thr, const double* area_rng_host, int n_area, void* workspace,
+                     size_t workspace_bytes, unsigned char* matched_out, unsigned char* ignored_out, int* npig_out,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ROIAlign — replaces `_C.roi_align_forward` / `_C.roi_align_backward`
  *   reference: csrc/ROIAlign.h:11-45, csrc/cpu/ROIAlign_cpu.cpp:114-257, csrc/cuda/ROIAlign_cuda.cu:65-254.
  * input  [B][H][W][C] NHWC, rois [R][5] = (batch_idx, x1, y1, x2, y2), output [R][PH][PW][C] NHWC.

@@ -964,31 +964,22 @@ def nchw3_to_nhwc4(x):
     return y
 
 
+def two_image_ends(r_cst, n_src):
+    """-> the `row_end` of two images, the first n_src of r_cst consistency rows the source's.  Any n_src is taken, as by the
+    native two-image entries (which this module does not call; tests/test_da_heads_multi_gpu.py does): above r_cst every row
+    is image 0's, below 0 image 1's"""
+    return min(max(int(n_src), 0), int(r_cst)), int(r_cst)
+
+
 def da_ins_tail_forward(h, w3, b3, labels, means, r_bce, r_cst, n_src):
     """h [r_bce + r_cst, C], w3 [C], b3 [1], labels float [r_bce] | None, means [L, 2] | None
-    -> (logits [rows], sums [2] = (BCE sum, consistency sum))"""
-    _dev(h, "h")
-    rows, C = h.shape
-    assert rows == r_bce + r_cst
-    L = int(means.shape[0]) if means is not None else 0
-    logits = torch.empty(rows, dtype=torch.float32, device=h.device)
-    sums = torch.zeros(2, dtype=torch.float32, device=h.device)
-    _lib.call("dadet_da_ins_tail_forward", _p(h), _p(w3), _p(b3), _p(labels), _p(means), _p(logits), _p(sums),
-              int(r_bce), int(r_cst), int(n_src), L, C, _stream())
-    return logits, sums
+    -> (logits [rows], sums [2] = (BCE sum, consistency sum)); two images, the first n_src consistency rows the source's"""
+    return da_ins_tail_forward_n(h, w3, b3, labels, means, r_bce, r_cst, two_image_ends(r_cst, n_src))
 
 
 def da_ins_tail_backward(h, w3, logits, labels, means, coef, inv_keep, r_bce, r_cst, n_src):
     """-> (g_z [rows, C] gradient w.r.t. the last hidden layer's PRE-activation, g_w3 [C], g_b3 [1], g_means [L, 2] | None)"""
-    rows, C = h.shape
-    L = int(means.shape[0]) if means is not None else 0
-    g_z = torch.empty_like(h)
-    acc = torch.zeros(C + 1 + 2 * L, dtype=torch.float32, device=h.device)      # one zero-fill for the three sums
-    g_w3, g_b3 = acc[:C], acc[C:C + 1]
-    g_means = acc[C + 1:].view(L, 2) if L else None
-    _lib.call("dadet_da_ins_tail_backward", _p(h), _p(w3), _p(logits), _p(labels), _p(means), _p(coef), float(inv_keep),
-              _p(g_z), _p(g_w3), _p(g_b3), _p(g_means), int(r_bce), int(r_cst), int(n_src), L, C, _stream())
-    return g_z, g_w3, g_b3, g_means
+    return da_ins_tail_backward_n(h, w3, logits, labels, means, coef, inv_keep, r_bce, r_cst, two_image_ends(r_cst, n_src))
 
 
 def _row_ends(row_end):

@@ -267,7 +267,6 @@ struct WgradGroup {
   WgradArgs a[kWgradGroupMax];
   int first[kWgradGroupMax + 1];
   int n;
-  int by_rows;      // 128 x 128 form: workgroups of one XCD take neighbouring tiles of the same rows
 };
 
 static_assert(plan::kCUs == kNumCU, "the plan layer's CU count");
@@ -283,7 +282,7 @@ int launch_wgrad_exact(WgradArgs& a, hipStream_t st);
 int launch_fwd_split(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st);    // conv_split.hip
 int launch_fwd_split_sk(ConvArgs& a, int fmt, hipStream_t st);
 int launch_wgrad_split(WgradArgs& a, bool small_map, int fmt, hipStream_t st);
-int launch_wgrad_split_group(const WgradArgs* a, int n, bool small_map, int by_rows, hipStream_t st);
+int launch_wgrad_split_group(const WgradArgs* a, int n, bool small_map, hipStream_t st);
 int launch_fwd_ws(ConvArgs& a, const plan::FwdPlan& p, int fmt, hipStream_t st);       // conv_ws.hip
 int launch_fwd_big(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st);               // conv_big.hip
 int launch_wgrad_big(WgradArgs& a, hipStream_t st);

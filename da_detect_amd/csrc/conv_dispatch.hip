@@ -416,7 +416,7 @@ extern "C" int dadet_conv_wgrad_group(const dadet_conv_desc* descs, int n, const
       w.out = static_cast<float*>(workspace[i]);
     }
   }
-  int rc = p.kind == 256 ? launch_wgrad_big_group(a, n, st) : launch_wgrad_split_group(a, n, p.small_map != 0, p.by_rows, st);
+  int rc = p.kind == 256 ? launch_wgrad_big_group(a, n, st) : launch_wgrad_split_group(a, n, p.small_map != 0, st);
   if (rc) return rc;
   for (int i = 0; i < n; ++i)
     if (p.splits[i] > 1)

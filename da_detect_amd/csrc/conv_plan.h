@@ -9,7 +9,6 @@
 //   DADET_BIG_GEMM              1        process  start-up value of the large-tile mode (dadet_set_big_gemm changes it)
 //   DADET_BIG_SPLITS            plan     call     forces the K parts of a large tile (1 .. 8); switches the tail cut off
 //   DADET_BIG_TILE_N            256      call     large-tile mode 2 only: 128 picks the 256 x 128 tile
-//   DADET_BIG_N256_WIDE         1        process  0: 129 .. 256 output channels stay on the 256 x 128 tile
 //   DADET_BIG_TAIL              1        call     0: no tail cut
 //   DADET_WS_1X1                1        call     0: no weight-stationary 1x1 kernel
 //   DADET_WS_K256_BN            128      call     64: K = 256 keeps 64-column panels
@@ -27,7 +26,6 @@
 //   DADET_WGRAD_BIG_SPLITS      plan     call     forces the parts of the 256 x 256 weight gradient
 //   DADET_WGRAD_GROUP_128       1        process  0: no grouped launch of the 128 x 128 weight gradient
 //   DADET_WGRAD_GROUP_ROWS      plan     call     forces the common rows per part of a grouped launch
-//   DADET_WGRAD_GROUP_BY_ROWS   1        process  0: the grouped 128 x 128 form maps workgroups as the single launch does
 //   DADET_ABLATE                0        process  profiling only: stage mask of the split kernel; no stream-K tail with it
 #pragma once
 #include <cstddef>
@@ -210,9 +208,8 @@ inline int big_variant(const dadet_conv_desc* d, const Gemm& g, bool epi_v4, int
   const int tm = cdiv(g.M, 256);
   // 129 .. 256 output channels over at least 96 row tiles (the pyramid's 256-channel 3x3 / lateral layers on P2 / P3,
   // M = 262144 / 65536): one column of 256 x 256 tiles fills the chip without any K split, on the kernel whose loop holds
-  // the matrix pipe 84% of the time instead of 61% (round 6; DADET_BIG_N256_WIDE=0: the 256 x 128 tile as before)
-  static const bool wide256 = !sw_off("DADET_BIG_N256_WIDE");
-  if (wide256 && d->Cout > 128 && d->Cout <= 256 && tm >= 96) return 1;
+  // the matrix pipe 84% of the time instead of 61% (round 6)
+  if (d->Cout > 128 && d->Cout <= 256 && tm >= 96) return 1;
   if (d->Cout <= 256) return tm * cdiv(d->Cout, 128) >= 96 ? 2 : 0;
   return tm * cdiv(d->Cout, 256) >= 96 ? 1 : 0;
 }
@@ -523,7 +520,6 @@ inline WgradPlan plan_wgrad(const dadet_conv_desc* d, int gy_ld, int gemm_mode, 
 struct WgradGroupPlan {
   int kind;             // 256 / 128: the tile of the grouped kernel; 0: no grouped launch
   int rows;             // rows per part, the same for every problem
-  int by_rows;          // 128 x 128 form: workgroups of one XCD take neighbouring tiles of the same rows
   int small_map;        // 128 x 128 form: the SMALL_MAP kernel (every problem's Wo < 32)
   int tiles_co[kGroupMax], tiles_kc[kGroupMax], splits[kGroupMax];
   size_t workspace_bytes[kGroupMax];
@@ -600,8 +596,6 @@ inline WgradGroupPlan plan_wgrad_group(const dadet_conv_desc* d, const int n, in
     // both grouped kernels park dense [splits][Cout][K] partial sums
     p.workspace_bytes[i] = p.splits[i] > 1 ? sizeof(float) * (size_t)p.splits[i] * d[i].Cout * d[i].KH * d[i].KW * d[i].Cin : 0;
   }
-  static const int by_rows = !sw_off("DADET_WGRAD_GROUP_BY_ROWS");
-  p.by_rows = tile == 256 ? 1 : by_rows;
   p.small_map = d[0].Wo < 32;
   return p;
 }

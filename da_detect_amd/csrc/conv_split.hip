@@ -908,9 +908,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_group_kernel(const Wg
   // one XCD: a contiguous range of (part, tile) pairs — the tiles of a part read the same operand rows (conv_wgrad_big_kernel's
   // order); the body's own remap of the tile index is then the identity's job
   const int T = g.a[i].tiles_co * g.a[i].tiles_kc;
-  const int lid = g.by_rows ? xcd_remap(local, T * g.a[i].splits) : local;
+  const int lid = xcd_remap(local, T * g.a[i].splits);
   const int split = lid / T;
-  wgrad_split_body<FMT, SMALL_MAP>(g.a[i], lid - split * T, split, g.by_rows != 0);
+  wgrad_split_body<FMT, SMALL_MAP>(g.a[i], lid - split * T, split, true);
 }
 
 template <int FMT, bool SMALL_MAP>
@@ -932,7 +932,7 @@ static int launch_wgrad_group_terms(const WgradGroup& g, hipStream_t st) {
 }
 
 // contraction mode 4 only; every problem on the same side of the small-map switch (the caller checks)
-int launch_wgrad_split_group(const WgradArgs* a, const int n, const bool small_map, const int by_rows, hipStream_t st) {
+int launch_wgrad_split_group(const WgradArgs* a, const int n, const bool small_map, hipStream_t st) {
   WgradGroup g;
   g.n = n;
   int at = 0;
@@ -942,7 +942,6 @@ int launch_wgrad_split_group(const WgradArgs* a, const int n, const bool small_m
     if (i < n) at += a[i].tiles_co * a[i].tiles_kc * a[i].splits;
   }
   g.first[kWgradGroupMax] = at;
-  g.by_rows = by_rows;
   return small_map ? launch_wgrad_group_terms<4, true>(g, st) : launch_wgrad_group_terms<4, false>(g, st);
 }
 

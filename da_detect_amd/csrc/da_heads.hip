@@ -22,6 +22,7 @@
 // FIXED order (per wavefront, per workgroup, then over the workgroups' partial sums by da_partials_sum_kernel): the same
 // inputs give the same bits on every run.
 #include "conv_common.h"   // amax_publish (contraction mode 4)
+#include <algorithm>
 #include <mutex>
 #include <unordered_map>
 
@@ -222,142 +223,19 @@ __global__ __launch_bounds__(256) void da_img_bwd_kernel(
 // h != 0 <=> gate open and mask = 1 / keep), fc3's weight / bias gradients and the gradient of the per-image means.
 // The two reversal weights act where the passes merge again, in da_ins_merge_kernel below.
 //   h       [R_bce + R_cst][C]   second hidden layer AFTER dropout
-//   means   [L][2]               per level: mean sigmoid of image 0 (source) and image 1 (target); null when R_cst == 0
+//   means   [L][num_images]      per level: mean sigmoid of each image (the reference: source, target); null when R_cst == 0
 //   sums    [2]                  += sum of BCE terms, += sum over consistency rows and levels of |mean - sigmoid|
-__global__ __launch_bounds__(256) void da_ins_fwd_kernel(const float* __restrict__ h, const float* __restrict__ w3,
-                                                         const float* __restrict__ b3,
-                                                         const float* __restrict__ labels,
-                                                         const float* __restrict__ means, float* __restrict__ logits,
-                                                         float* __restrict__ sums, float* __restrict__ partials,
-                                                         int R_bce, int R_cst, int n_src, int L, int C) {
-  // (sums in a fixed order, as in da_img_fwd_kernel: partials[block][2], or — no scratch — atomics into sums)
-  __shared__ float s_acc[4][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wave_global = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int nwaves = (gridDim.x * blockDim.x) >> 6;
-  const int R = R_bce + R_cst;
-  const float bias = b3[0];
-  float bce = 0.f, cst = 0.f;
-  for (int r = wave_global; r < R; r += nwaves) {
-    const float* row = h + (size_t)r * C;
-    float dot = 0.f;
-    for (int c = lane * 4; c < C; c += 256) {
-      const float4 hv = *reinterpret_cast<const float4*>(row + c);
-      const float4 wv = *reinterpret_cast<const float4*>(w3 + c);
-      dot += hv.x * wv.x + hv.y * wv.y + hv.z * wv.z + hv.w * wv.w;
-    }
-    const float logit = wave_sum(dot) + bias;
-    if (lane == 0) {
-      logits[r] = logit;
-      if (r < R_bce) {
-        bce += bce_with_logits(logit, labels[r]);
-      } else {
-        const int img = (r - R_bce) < n_src ? 0 : 1;
-        const float sg = sigmoidf(logit);
-        for (int l = 0; l < L; ++l) cst += fabsf(means[l * 2 + img] - sg);
-      }
-    }
-  }
-  if (lane == 0) {
-    s_acc[wave][0] = bce;
-    s_acc[wave][1] = cst;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const float v = ((s_acc[0][threadIdx.x] + s_acc[1][threadIdx.x]) + s_acc[2][threadIdx.x]) + s_acc[3][threadIdx.x];
-    if (partials) partials[(size_t)blockIdx.x * 2 + threadIdx.x] = v;
-    else if (v != 0.f) atomicAdd(&sums[threadIdx.x], v);
-  }
-}
-
-// coef[0] = d loss / d (BCE sum), coef[1] = d loss / d (consistency sum) (device scalars: upstream gradients x the
-// mean factors).  g_z[r][c] = dlogit_r * w3[c] * inv_keep * [h[r][c] != 0];  g_w3[c] += sum_r dlogit_r * h[r][c];
-// g_b3 += sum_r dlogit_r;  g_means[l][img] += coef[1] * sign(mean - sigmoid).
-__global__ __launch_bounds__(256) void da_ins_bwd_kernel(const float* __restrict__ h, const float* __restrict__ w3,
-                                                         const float* __restrict__ logits,
-                                                         const float* __restrict__ labels,
-                                                         const float* __restrict__ means,
-                                                         const float* __restrict__ coef, float inv_keep,
-                                                         float* __restrict__ g_z, float* __restrict__ g_w3,
-                                                         float* __restrict__ g_b3, float* __restrict__ g_means,
-                                                         int R_bce, int R_cst, int n_src, int L, int C) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* s_w = reinterpret_cast<float*>(smem);   // [C] workgroup partial of g_w3, then [L * 2] of g_means, [1] g_b3
-  float* s_m = s_w + C;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nw_block = blockDim.x >> 6;
-  for (int c = threadIdx.x; c < C + 2 * L + 1; c += blockDim.x) s_w[c] = 0.f;
-  __syncthreads();
-  const int R = R_bce + R_cst;
-  const float a_bce = coef[0], a_cst = coef[1];
-  float4 wacc[4];     // C <= 1024: lane owns float4 slots c = lane*4 + 256*k
-#pragma unroll
-  for (int k = 0; k < 4; ++k) wacc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  float bacc = 0.f;
-  for (int r = blockIdx.x * nw_block + wave; r < R; r += gridDim.x * nw_block) {
-    const float sg = sigmoidf(logits[r]);
-    float dl;
-    if (r < R_bce) {
-      dl = a_bce * (sg - labels[r]);
-    } else {
-      const int img = (r - R_bce) < n_src ? 0 : 1;
-      float sgn = 0.f;    // d |m - s| / d s summed over levels
-      for (int l = 0; l < L; ++l) {
-        const float d = means[l * 2 + img] - sg;
-        const float sd = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        sgn -= sd;
-        if (lane == 0 && sd != 0.f) atomicAdd(&s_m[l * 2 + img], a_cst * sd);
-      }
-      dl = a_cst * sgn * sg * (1.f - sg);
-    }
-    bacc += dl;
-    const float* row = h + (size_t)r * C;
-    const float gk = dl * inv_keep;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = lane * 4 + 256 * k;
-      if (c < C) {
-        const float4 hv = *reinterpret_cast<const float4*>(row + c);
-        const float4 wv = *reinterpret_cast<const float4*>(w3 + c);
-        float4 o;
-        o.x = hv.x != 0.f ? gk * wv.x : 0.f; o.y = hv.y != 0.f ? gk * wv.y : 0.f;
-        o.z = hv.z != 0.f ? gk * wv.z : 0.f; o.w = hv.w != 0.f ? gk * wv.w : 0.f;
-        *reinterpret_cast<float4*>(g_z + (size_t)r * C + c) = o;
-        wacc[k].x += dl * hv.x; wacc[k].y += dl * hv.y; wacc[k].z += dl * hv.z; wacc[k].w += dl * hv.w;
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = lane * 4 + 256 * k;
-    if (c < C) {
-      atomicAdd(&s_w[c + 0], wacc[k].x);
-      atomicAdd(&s_w[c + 1], wacc[k].y);
-      atomicAdd(&s_w[c + 2], wacc[k].z);
-      atomicAdd(&s_w[c + 3], wacc[k].w);
-    }
-  }
-  if (lane == 0 && bacc != 0.f) atomicAdd(&s_m[2 * L], bacc);   // bacc is wavefront-uniform
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x)
-    if (s_w[c] != 0.f) atomicAdd(&g_w3[c], s_w[c]);
-  if (g_means && threadIdx.x < 2 * L && s_m[threadIdx.x] != 0.f) atomicAdd(&g_means[threadIdx.x], s_m[threadIdx.x]);
-  if (threadIdx.x == 0 && s_m[2 * L] != 0.f) atomicAdd(g_b3, s_m[2 * L]);
-}
-
-// ---- the same tail for any number of images --------------------------------------------------------
 // Consistency rows are stacked image by image; image i owns rows [row_end[i-1], row_end[i]) of the R_cst consistency rows
 // (an image may own none).  The ends are known on the host and travel BY VALUE with the launch (no device buffer, no copy);
 // the workgroup keeps them in LDS and every wavefront finds its row's image from them: its rows ascend, so the image index
-// only ever moves forward.  means / g_means are [L][num_images].  Everything else — one wavefront per row, float4 along
-// the hidden units, the fixed order of the forward sums, the LDS accumulators of the backward — is da_ins_fwd_kernel /
-// da_ins_bwd_kernel, and for two images with ends {n_src, R_cst} the forward gives the same bits.
+// only ever moves forward.  The reference's batch of two (ROIs of the source image first) is the table {n_src, R_cst}.
 constexpr int kDaInsMaxImg = 64;         // images per launch (the by-value table of segment ends)
 constexpr int kDaInsMaxMeans = 512;      // levels x images whose gradient sums the backward keeps in LDS
 struct DaRowEnds {
   int end[kDaInsMaxImg];
 };
 
+// (sums in a fixed order, as in da_img_fwd_kernel: partials[block][2], or — no scratch — atomics into sums)
 __global__ __launch_bounds__(256) void da_ins_fwd_n_kernel(const float* __restrict__ h, const float* __restrict__ w3,
                                                            const float* __restrict__ b3,
                                                            const float* __restrict__ labels,
@@ -408,6 +286,9 @@ __global__ __launch_bounds__(256) void da_ins_fwd_n_kernel(const float* __restri
   }
 }
 
+// coef[0] = d loss / d (BCE sum), coef[1] = d loss / d (consistency sum) (device scalars: upstream gradients x the
+// mean factors).  g_z[r][c] = dlogit_r * w3[c] * inv_keep * [h[r][c] != 0];  g_w3[c] += sum_r dlogit_r * h[r][c];
+// g_b3 += sum_r dlogit_r;  g_means[l][img] += coef[1] * sign(mean - sigmoid).
 // LDS: [C] workgroup partial of g_w3, [L * NI] of g_means, [1] of g_b3
 __global__ __launch_bounds__(256) void da_ins_bwd_n_kernel(const float* __restrict__ h, const float* __restrict__ w3,
                                                            const float* __restrict__ logits,
@@ -719,45 +600,8 @@ extern "C" int dadet_triplet_w_backward(const float* anchor, const float* positi
   return check_launch("triplet_w_backward");
 }
 
-extern "C" int dadet_da_ins_tail_forward(const float* h, const float* w3, const float* b3, const float* labels,
-                                         const float* means, float* logits, float* sums, int R_bce, int R_cst,
-                                         int n_src, int levels, int C, void* stream) {
-  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && levels >= 0, "da_ins_tail_forward: bad dims");
-  if (R_bce + R_cst == 0) return DADET_OK;
-  DADET_REQUIRE(h && w3 && b3 && logits && sums && a16(h) && a16(w3) && (R_bce == 0 || labels) &&
-                    (R_cst == 0 || (means && levels > 0)),
-                "da_ins_tail_forward: bad pointers");
-  int blocks = ceil_div(R_bce + R_cst, 4);
-  if (blocks > kNumCU * 2) blocks = kNumCU * 2;
-  float* partials = da_partials(as_stream(stream));
-  hipLaunchKernelGGL(da_ins_fwd_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), h, w3, b3, labels, means,
-                     logits, sums, partials, R_bce, R_cst, n_src, levels, C);
-  if (partials)
-    hipLaunchKernelGGL(da_partials_sum_kernel, dim3(2), dim3(256), 0, as_stream(stream), partials, blocks, 2, sums);
-  return check_launch("da_ins_tail_forward");
-}
-
-extern "C" int dadet_da_ins_tail_backward(const float* h, const float* w3, const float* logits, const float* labels,
-                                          const float* means, const float* coef, float inv_keep, float* g_z,
-                                          float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst, int n_src,
-                                          int levels, int C, void* stream) {
-  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && C <= 1024 && levels >= 0 && levels <= 16,
-                "da_ins_tail_backward: C must be a multiple of 4 and <= 1024");
-  if (R_bce + R_cst == 0) return DADET_OK;
-  DADET_REQUIRE(h && w3 && logits && coef && g_z && g_w3 && g_b3 && a16(h) && a16(w3) && a16(g_z) &&
-                    (R_bce == 0 || labels) && (R_cst == 0 || (means && levels > 0)),
-                "da_ins_tail_backward: bad pointers");
-  int blocks = ceil_div(R_bce + R_cst, 4 * 4);
-  if (blocks > kNumCU) blocks = kNumCU;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(da_ins_bwd_kernel, dim3(blocks), dim3(256), sizeof(float) * (C + 2 * levels + 1), as_stream(stream),
-                     h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3, g_means, R_bce, R_cst, n_src, levels,
-                     C);
-  return check_launch("da_ins_tail_backward");
-}
-
-// the segment ends of the `_n` entry points: host array -> by-value table; false when they are not a non-decreasing walk
-// from >= 0 to R_cst
+// the segment ends of the instance tail: host array -> by-value table; false when they are not a non-decreasing walk from
+// >= 0 to R_cst
 static bool da_row_ends(const int* row_end, int num_images, int R_cst, DaRowEnds* out) {
   int prev = 0;
   for (int i = 0; i < num_images; ++i) {
@@ -768,19 +612,19 @@ static bool da_row_ends(const int* row_end, int num_images, int R_cst, DaRowEnds
   return prev == R_cst;
 }
 
-extern "C" int dadet_da_ins_tail_forward_n(const float* h, const float* w3, const float* b3, const float* labels,
-                                           const float* means, float* logits, float* sums, int R_bce, int R_cst,
-                                           const int* row_end, int num_images, int levels, int C, void* stream) {
-  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && levels >= 0, "da_ins_tail_forward_n: bad dims");
+// the instance tail behind both pairs of entry points; `who` is the entry that was called, for the error texts
+static int da_ins_tail_forward(const char* who, const float* h, const float* w3, const float* b3, const float* labels,
+                               const float* means, float* logits, float* sums, int R_bce, int R_cst, const int* row_end,
+                               int num_images, int levels, int C, void* stream) {
+  DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && levels >= 0, "%s: bad dims", who);
   DADET_REQUIRE(num_images >= 1 && num_images <= kDaInsMaxImg && row_end,
-                "da_ins_tail_forward_n: num_images must be in 1..64, with its row segment ends");
+                "%s: num_images must be in 1..64, with its row segment ends", who);
   DaRowEnds ends;
-  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends),
-                "da_ins_tail_forward_n: row_end must ascend from >= 0 and end at R_cst");
+  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends), "%s: row_end must ascend from >= 0 and end at R_cst", who);
   if (R_bce + R_cst == 0) return DADET_OK;
   DADET_REQUIRE(h && w3 && b3 && logits && sums && a16(h) && a16(w3) && (R_bce == 0 || labels) &&
                     (R_cst == 0 || (means && levels > 0)),
-                "da_ins_tail_forward_n: bad pointers");
+                "%s: bad pointers", who);
   int blocks = ceil_div(R_bce + R_cst, 4);
   if (blocks > kNumCU * 2) blocks = kNumCU * 2;
   float* partials = da_partials(as_stream(stream));
@@ -788,33 +632,65 @@ extern "C" int dadet_da_ins_tail_forward_n(const float* h, const float* w3, cons
                      logits, sums, partials, R_bce, R_cst, ends, num_images, levels, C);
   if (partials)
     hipLaunchKernelGGL(da_partials_sum_kernel, dim3(2), dim3(256), 0, as_stream(stream), partials, blocks, 2, sums);
-  return check_launch("da_ins_tail_forward_n");
+  return check_launch(who);
 }
 
-extern "C" int dadet_da_ins_tail_backward_n(const float* h, const float* w3, const float* logits, const float* labels,
-                                            const float* means, const float* coef, float inv_keep, float* g_z,
-                                            float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst,
-                                            const int* row_end, int num_images, int levels, int C, void* stream) {
+static int da_ins_tail_backward(const char* who, const float* h, const float* w3, const float* logits,
+                                const float* labels, const float* means, const float* coef, float inv_keep, float* g_z,
+                                float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst, const int* row_end,
+                                int num_images, int levels, int C, void* stream) {
   DADET_REQUIRE(R_bce >= 0 && R_cst >= 0 && C > 0 && C % 4 == 0 && C <= 1024 && levels >= 0 && levels <= 16,
-                "da_ins_tail_backward_n: C must be a multiple of 4 and <= 1024, levels <= 16");
+                "%s: C must be a multiple of 4 and <= 1024, levels <= 16", who);
   DADET_REQUIRE(num_images >= 1 && num_images <= kDaInsMaxImg && row_end,
-                "da_ins_tail_backward_n: num_images must be in 1..64, with its row segment ends");
-  DADET_REQUIRE(levels * num_images <= kDaInsMaxMeans,
-                "da_ins_tail_backward_n: levels x num_images exceeds the 512 sums kept in LDS");
+                "%s: num_images must be in 1..64, with its row segment ends", who);
+  DADET_REQUIRE(levels * num_images <= kDaInsMaxMeans, "%s: levels x num_images exceeds the 512 sums kept in LDS", who);
   DaRowEnds ends;
-  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends),
-                "da_ins_tail_backward_n: row_end must ascend from >= 0 and end at R_cst");
+  DADET_REQUIRE(da_row_ends(row_end, num_images, R_cst, &ends), "%s: row_end must ascend from >= 0 and end at R_cst", who);
   if (R_bce + R_cst == 0) return DADET_OK;
   DADET_REQUIRE(h && w3 && logits && coef && g_z && g_w3 && g_b3 && a16(h) && a16(w3) && a16(g_z) &&
                     (R_bce == 0 || labels) && (R_cst == 0 || (means && levels > 0)),
-                "da_ins_tail_backward_n: bad pointers");
+                "%s: bad pointers", who);
   int blocks = ceil_div(R_bce + R_cst, 4 * 4);
   if (blocks > kNumCU) blocks = kNumCU;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(da_ins_bwd_n_kernel, dim3(blocks), dim3(256), sizeof(float) * (C + levels * num_images + 1),
                      as_stream(stream), h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3, g_means, R_bce,
                      R_cst, ends, num_images, levels, C);
-  return check_launch("da_ins_tail_backward_n");
+  return check_launch(who);
+}
+
+// two images, the first n_src consistency rows the source image's.  Any n_src is taken: above R_cst every row is image 0's,
+// below 0 every row is image 1's.
+extern "C" int dadet_da_ins_tail_forward(const float* h, const float* w3, const float* b3, const float* labels,
+                                         const float* means, float* logits, float* sums, int R_bce, int R_cst,
+                                         int n_src, int levels, int C, void* stream) {
+  const int row_end[2] = {std::min(std::max(n_src, 0), R_cst), R_cst};
+  return da_ins_tail_forward("da_ins_tail_forward", h, w3, b3, labels, means, logits, sums, R_bce, R_cst, row_end, 2,
+                             levels, C, stream);
+}
+
+extern "C" int dadet_da_ins_tail_backward(const float* h, const float* w3, const float* logits, const float* labels,
+                                          const float* means, const float* coef, float inv_keep, float* g_z,
+                                          float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst, int n_src,
+                                          int levels, int C, void* stream) {
+  const int row_end[2] = {std::min(std::max(n_src, 0), R_cst), R_cst};
+  return da_ins_tail_backward("da_ins_tail_backward", h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3,
+                              g_means, R_bce, R_cst, row_end, 2, levels, C, stream);
+}
+
+extern "C" int dadet_da_ins_tail_forward_n(const float* h, const float* w3, const float* b3, const float* labels,
+                                           const float* means, float* logits, float* sums, int R_bce, int R_cst,
+                                           const int* row_end, int num_images, int levels, int C, void* stream) {
+  return da_ins_tail_forward("da_ins_tail_forward_n", h, w3, b3, labels, means, logits, sums, R_bce, R_cst, row_end,
+                             num_images, levels, C, stream);
+}
+
+extern "C" int dadet_da_ins_tail_backward_n(const float* h, const float* w3, const float* logits, const float* labels,
+                                            const float* means, const float* coef, float inv_keep, float* g_z,
+                                            float* g_w3, float* g_b3, float* g_means, int R_bce, int R_cst,
+                                            const int* row_end, int num_images, int levels, int C, void* stream) {
+  return da_ins_tail_backward("da_ins_tail_backward_n", h, w3, logits, labels, means, coef, inv_keep, g_z, g_w3, g_b3,
+                              g_means, R_bce, R_cst, row_end, num_images, levels, C, stream);
 }
 
 extern "C" int dadet_da_ins_dropout_rows(const float* h1, const float* masks, float* out, int64_t numel_per_pass,

@@ -127,6 +127,32 @@ class _RPNLoss(Function):
         return g_obj * g0, g_reg * g1, None, None, None, None, None
 
 
+def _rpn_head_rows_core(rows, g0, g1, t_rows, x_cols, w3, wc, wb, A):
+    """The single-conv RPN head's backward on S gathered rows, between a node's gather and its scatter: rows [S, ldg] the
+    loss kernel's row-form gradient, t_rows [S, C, 1, 1] the hidden activations and x_cols [S, k*k*C, 1, 1] the 3x3 operand
+    rows at the rows' pixels -> (dw3, db3, d_head [ldg, C, 1, 1], b_head [ldg], y [S, k*k*C, 1, 1] the data gradient per tap)"""
+    S, ldg = rows.shape
+    C, k = w3.shape[1], w3.shape[2]
+    # upstream factors of the two losses (1 and 1 when they enter the total loss unweighted)
+    scale = torch.cat([g0.reshape(1).expand(A), g1.reshape(1).expand(4 * A), rows.new_zeros(ldg - 5 * A)])
+    G = (rows * scale).view(S, ldg, 1, 1)
+    # the two 1x1 heads as one [5A (+pad), C] matrix, like the forward pass (layers.conv1x1_multi)
+    w_head = torch.cat([wc.reshape(A, C), wb.reshape(4 * A, C), rows.new_zeros(ldg - 5 * A, C)], 0)
+    d_head = _C.conv_wgrad(t_rows, G, (ldg, C, 1, 1))
+    b_head = G.view(S, ldg).sum(0)
+    # gradient of the hidden activations at the rows' pixels, gated by the ReLU (relu_mode 2: mask_ref > 0)
+    gt = _C.conv_forward(G, w_head.t().contiguous().view(C, ldg, 1, 1), relu_mode=2, mask_ref=t_rows)
+    dw3 = _C.conv_wgrad(x_cols, gt, (w3.shape[0], k * k * C, 1, 1))
+    dw3 = dw3.view(w3.shape[0], k, k, C).permute(0, 3, 1, 2)          # the parameter's channels_last layout
+    db3 = gt.view(S, -1).sum(0)
+    # data gradient: y[r][tap][ci] = sum_co gt[r][co] * w3[co][tap][ci], added at pixel_r + tap offset
+    # W^T [K, Cout]: the 3x3 weight viewed as a 1x1 convolution over K = (tap, ci) and transposed — through the
+    # per-step cache of transposed weights (one batched launch per optimizer step) instead of a 38 MB copy here
+    w_1x1 = w3.permute(0, 2, 3, 1).reshape(w3.shape[0], k * k * C, 1, 1)
+    y = _C.conv_forward(gt, _C.conv_weight_transpose(w_1x1))
+    return dw3, db3, d_head, b_head, y
+
+
 class _RPNHeadLossRows(Function):
     """RPN losses of one level AND the single-conv RPN head's whole backward, on the sampled rows only.
 
@@ -154,31 +180,15 @@ class _RPNHeadLossRows(Function):
     @once_differentiable
     def backward(ctx, g0, g1):
         x, w3, wc, wb, t, rows, pixels = ctx.saved_tensors
-        A, S, ldg = ctx.A, rows.shape[0], rows.shape[1]
+        A, S = ctx.A, rows.shape[0]
         C = x.shape[1]
         k = w3.shape[2]
-        # upstream factors of the two losses (1 and 1 when they enter the total loss unweighted)
-        scale = torch.cat([g0.reshape(1).expand(A), g1.reshape(1).expand(4 * A), rows.new_zeros(ldg - 5 * A)])
-        G = (rows * scale).view(S, ldg, 1, 1)
         # (gathered rows are bounded by their map's largest magnitude; views are new objects: handed on by hand, amax.py)
         t_rows = _C.gather_pixel_taps(t, pixels)
         t_rows = _amax.carry(t_rows.view(S, C, 1, 1), t_rows)
         x_cols = _C.gather_pixel_taps(x, pixels, k, k // 2)
         x_cols = _amax.carry(x_cols.view(S, k * k * C, 1, 1), x_cols)
-        # the two 1x1 heads as one [5A (+pad), C] matrix, like the forward pass (layers.conv1x1_multi)
-        w_head = torch.cat([wc.reshape(A, C), wb.reshape(4 * A, C), rows.new_zeros(ldg - 5 * A, C)], 0)
-        d_head = _C.conv_wgrad(t_rows, G, (ldg, C, 1, 1))
-        b_head = G.view(S, ldg).sum(0)
-        # gradient of the hidden activations at the rows' pixels, gated by the ReLU (relu_mode 2: mask_ref > 0)
-        gt = _C.conv_forward(G, w_head.t().contiguous().view(C, ldg, 1, 1), relu_mode=2, mask_ref=t_rows)
-        dw3 = _C.conv_wgrad(x_cols, gt, (w3.shape[0], k * k * C, 1, 1))
-        dw3 = dw3.view(w3.shape[0], k, k, C).permute(0, 3, 1, 2)          # the parameter's channels_last layout
-        db3 = gt.view(S, -1).sum(0)
-        # data gradient: y[r][tap][ci] = sum_co gt[r][co] * w3[co][tap][ci], added at pixel_r + tap offset
-        # W^T [K, Cout]: the 3x3 weight viewed as a 1x1 convolution over K = (tap, ci) and transposed — through the
-        # per-step cache of transposed weights (one batched launch per optimizer step) instead of a 38 MB copy here
-        w_1x1 = w3.permute(0, 2, 3, 1).reshape(w3.shape[0], k * k * C, 1, 1)
-        y = _C.conv_forward(gt, _C.conv_weight_transpose(w_1x1))
+        dw3, db3, d_head, b_head, y = _rpn_head_rows_core(rows, g0, g1, t_rows, x_cols, w3, wc, wb, A)
         dx = _C.scatter_pixel_taps_add(y.view(S, k * k, C), pixels, tuple(x.shape), k, k // 2)
         return (dx, dw3, db3, d_head[:A], b_head[:A], d_head[A:5 * A], b_head[A:5 * A]) + (None,) * 9
 
@@ -225,27 +235,18 @@ class _RPNHeadLossRowsPyramid(Function):
         w3, wc, wb, rows, pixels, row_level = saved[:6]
         A, L = ctx.A, ctx.L
         xs, ts = saved[6:6 + L], saved[6 + L:6 + 2 * L]
-        S, ldg = rows.shape
+        S = rows.shape[0]
         C = xs[0].shape[1]
         k = w3.shape[2]
-        scale = torch.cat([g0.reshape(1).expand(A), g1.reshape(1).expand(4 * A), rows.new_zeros(ldg - 5 * A)])
-        G = (rows * scale).view(S, ldg, 1, 1)
         # (zero-filled: a row no level claims — there is none — must not put uninitialised memory next to its zero G row)
         t_rows = torch.zeros((S, 1, C), dtype=torch.float32, device=rows.device)
         x_cols = torch.zeros((S, k * k, C), dtype=torch.float32, device=rows.device)
         for lvl in range(L):
             _C.gather_pixel_taps(ts[lvl], pixels, row_level=row_level, level=lvl, out=t_rows)
             _C.gather_pixel_taps(xs[lvl], pixels, k, k // 2, row_level=row_level, level=lvl, out=x_cols)
-        t_rows, x_cols = t_rows.view(S, C, 1, 1), x_cols.view(S, k * k * C, 1, 1)
-        w_head = torch.cat([wc.reshape(A, C), wb.reshape(4 * A, C), rows.new_zeros(ldg - 5 * A, C)], 0)
-        d_head = _C.conv_wgrad(t_rows, G, (ldg, C, 1, 1))
-        b_head = G.view(S, ldg).sum(0)
-        gt = _C.conv_forward(G, w_head.t().contiguous().view(C, ldg, 1, 1), relu_mode=2, mask_ref=t_rows)
-        dw3 = _C.conv_wgrad(x_cols, gt, (w3.shape[0], k * k * C, 1, 1))
-        dw3 = dw3.view(w3.shape[0], k, k, C).permute(0, 3, 1, 2)
-        db3 = gt.view(S, -1).sum(0)
-        w_1x1 = w3.permute(0, 2, 3, 1).reshape(w3.shape[0], k * k * C, 1, 1)
-        y = _C.conv_forward(gt, _C.conv_weight_transpose(w_1x1)).view(S, k * k, C)
+        dw3, db3, d_head, b_head, y = _rpn_head_rows_core(rows, g0, g1, t_rows.view(S, C, 1, 1),
+                                                          x_cols.view(S, k * k * C, 1, 1), w3, wc, wb, A)
+        y = y.view(S, k * k, C)
         dxs = [_C.scatter_pixel_taps_add(y, pixels, tuple(xs[lvl].shape), k, k // 2, row_level=row_level, level=lvl)
                for lvl in range(L)]
         return (dw3, db3, d_head[:A], b_head[:A], d_head[A:5 * A], b_head[A:5 * A]) + (None,) * 6 + tuple(dxs) + \

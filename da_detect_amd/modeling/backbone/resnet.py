@@ -88,6 +88,67 @@ class _WgradGroup(object):
         self.reqs = []
 
 
+class _BlockBackward(object):
+    """What the backward passes of _BottleneckFn and _DCNBottleneckFn share, around the 3x3's own gradient.
+
+    `open`: S3 (the output's ReLU gate, unless the consumer gated already), the lane, the batched reduction and the grouped
+    launch for the block's weight gradients, conv3's weight gradient and S2.  `close`, once the node has S1: the weight
+    gradients of conv1 and of the shortcut, the grouped launch and the reduction pass, then dX.  The native calls are issued
+    in this order in both nodes; the lane's stream schedule depends on it.  The constructor launches nothing."""
+
+    def __init__(self, needs, x, w1, wd, s1, sd, stride):
+        self.need_x, self.n1, self.n2, self.n3, nd = needs
+        self.nd = nd and wd is not None
+        self.x, self.w1, self.wd, self.s1, self.sd, self.stride = x, w1, wd, s1, sd, stride
+
+    def open(self, G, out, out_private, y2, w2, w3, s3):
+        """-> (S2, dw3)"""
+        self.S3 = G.contiguous(memory_format=torch.channels_last) if out_private else _C.relu_bn_backward(G, out, None)[1]
+        self.lane = WgradLane(G.device, rows=G.shape[0] * G.shape[2] * G.shape[3])
+        # the block's 3 - 4 weight gradients share ONE reduction launch over their split partial results (_WGRAD_BATCH)
+        self.batch = _C.WgradBatch() if _WGRAD_BATCH else None
+        weights = ((w3, self.n3), (w2, self.n2), (self.w1, self.n1), (self.wd, self.nd))
+        self.group = _WgradGroup(self.lane, self.batch, [w for w, need in weights if need])
+        dw3 = self.wgrad(w3, y2, self.S3, 1, 0, s3) if self.n3 else None
+        return _C.conv_forward(self.S3, _C.conv_weight_transpose(w3, s3), relu_mode=2, mask_ref=y2), dw3
+
+    def wgrad(self, w, xin, gout, st, pd, sc, shape=None, grouped=True):
+        """w's gradient: a member of the grouped launch (-> None: it lands in w's gradient buffer), or on the lane"""
+        shape = tuple(w.shape) if shape is None else shape
+        batch = self.batch
+        if grouped and self.group.take(w, xin, gout, st, pd, sc, shape=shape):
+            return None
+        return self.lane.run_into(w, lambda acc: _C.conv_wgrad(xin, gout, shape, st, pd, out_scale=sc, dw=acc,
+                                                               accumulate=True, pending=batch),
+                                  lambda: _C.conv_wgrad(xin, gout, shape, st, pd, out_scale=sc, pending=batch),
+                                  xin, gout)
+
+    def close(self, S1, in_relu):
+        """-> (dx, dw1, dwd)"""
+        x, w1, wd, s1, sd, stride, S3 = self.x, self.w1, self.wd, self.s1, self.sd, self.stride, self.S3
+        dw1 = dwd = dx = None
+        if self.n1:
+            dw1 = self.wgrad(w1, x, S1, stride, 0, s1)
+        if self.nd:
+            dwd = self.wgrad(wd, x, S3, stride, 0, sd)
+        self.group.issue()
+        self.lane.reduce_batch(self.batch)
+        if self.need_x:
+            gate = dict(relu_mode=2, mask_ref=x) if in_relu else {}
+            hw = tuple(x.shape[2:])
+            if wd is None:
+                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=S3, **gate)
+            elif stride == 1:
+                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd))
+                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t, **gate)
+            else:  # both 1x1 stride-s data gradients scatter onto the same (s*h, s*w) lattice of a zero map
+                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd), out_spatial_stride=stride, out_hw=hw)
+                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t,
+                                     out_spatial_stride=stride, out_hw=hw, **gate)
+        self.lane.join()
+        return dx, dw1, dwd
+
+
 class _BottleneckFn(torch.autograd.Function):
     """One bottleneck (resnet.py:294-314) as ONE autograd node with a hand-scheduled backward.
 
@@ -116,52 +177,15 @@ class _BottleneckFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, G):
         x, y1, y2, out, w1, w2, w3, wd, s1, s2, s3, sd = ctx.saved_tensors
-        need_x, n1, n2, n3, nd = ctx.needs_input_grad[:5]
-        stride = ctx.stride
-        S3 = G.contiguous(memory_format=torch.channels_last) if ctx.out_private else \
-            _C.relu_bn_backward(G, out, None)[1]
-        dw1 = dw2 = dw3 = dwd = dx = None
-        lane = WgradLane(G.device, rows=G.shape[0] * G.shape[2] * G.shape[3])
-        # the block's 3 - 4 weight gradients share ONE reduction launch over their split partial results (_WGRAD_BATCH)
-        batch = _C.WgradBatch() if _WGRAD_BATCH else None
-
-        group = _WgradGroup(lane, batch, [w for w, need in ((w3, n3), (w2, n2), (w1, n1), (wd, nd and wd is not None))
-                                          if need])
-
-        def wgrad(w, xin, gout, st, pd, sc):
-            if group.take(w, xin, gout, st, pd, sc):
-                return None
-            return lane.run_into(w, lambda acc: _C.conv_wgrad(xin, gout, tuple(w.shape), st, pd, out_scale=sc, dw=acc,
-                                                              accumulate=True, pending=batch),
-                                 lambda: _C.conv_wgrad(xin, gout, tuple(w.shape), st, pd, out_scale=sc, pending=batch),
-                                 xin, gout)
-
-        if n3:
-            dw3 = wgrad(w3, y2, S3, 1, 0, s3)
-        S2 = _C.conv_forward(S3, _C.conv_weight_transpose(w3, s3), relu_mode=2, mask_ref=y2)
+        need_x, n1, n2 = ctx.needs_input_grad[:3]
+        b = _BlockBackward(ctx.needs_input_grad[:5], x, w1, wd, s1, sd, ctx.stride)
+        S2, dw3 = b.open(G, out, ctx.out_private, y2, w2, w3, s3)
+        dw2 = S1 = None
         if n2:
-            dw2 = wgrad(w2, y1, S2, 1, 1, s2)
+            dw2 = b.wgrad(w2, y1, S2, 1, 1, s2)
         if n1 or need_x:
             S1 = _C.conv_forward(S2, _C.conv_weight_transpose(w2, s2), pad=1, relu_mode=2, mask_ref=y1)
-        if n1:
-            dw1 = wgrad(w1, x, S1, stride, 0, s1)
-        if nd and wd is not None:
-            dwd = wgrad(wd, x, S3, stride, 0, sd)
-        group.issue()
-        lane.reduce_batch(batch)
-        if need_x:
-            gate = dict(relu_mode=2, mask_ref=x) if ctx.in_relu else {}
-            hw = tuple(x.shape[2:])
-            if wd is None:
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=S3, **gate)
-            elif stride == 1:
-                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd))
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t, **gate)
-            else:  # both 1x1 stride-s data gradients scatter onto the same (s*h, s*w) lattice of a zero map
-                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd), out_spatial_stride=stride, out_hw=hw)
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t,
-                                     out_spatial_stride=stride, out_hw=hw, **gate)
-        lane.join()
+        dx, dw1, dwd = b.close(S1, ctx.in_relu)
         return (dx, dw1, dw2, dw3, dwd) + (None,) * 11
 
 
@@ -202,64 +226,28 @@ class _DCNBottleneckFn(torch.autograd.Function):
     def backward(ctx, G):
         x, y1, om, cols, y2, out, w1, w2, w3, wd, w_off, s1, s2, s3, sd = ctx.saved_tensors
         stride, in_relu, out_private, modulated, dg, kh, kw, n_offch, n_offpad = ctx.conf
-        need_x, n1, n2, n3, nd, n_off, n_boff = ctx.needs_input_grad[:7]
+        n2, n_off, n_boff = ctx.needs_input_grad[2], ctx.needs_input_grad[5], ctx.needs_input_grad[6]
         cout2, cin2 = w2.shape[0], w2.shape[1]
-        S3 = G.contiguous(memory_format=torch.channels_last) if out_private else _C.relu_bn_backward(G, out, None)[1]
-        dw1 = dw2 = dw3 = dwd = dx = dwo = dbo = None
-        lane = WgradLane(G.device, rows=G.shape[0] * G.shape[2] * G.shape[3])
-        batch = _C.WgradBatch() if _WGRAD_BATCH else None
-
-        # (the offset branch's gradient has rows padded beyond its 18 | 27 channels: not a member of the grouped launch)
-        group = _WgradGroup(lane, batch, [w for w, need in ((w3, n3), (w2, n2), (w1, n1), (wd, nd and wd is not None))
-                                          if need])
-
-        def wgrad(w, xin, gout, st, pd, sc, shape=None):
-            shape = tuple(w.shape) if shape is None else shape
-            if w is not w_off and group.take(w, xin, gout, st, pd, sc, shape=shape):
-                return None
-            return lane.run_into(w, lambda acc: _C.conv_wgrad(xin, gout, shape, st, pd, out_scale=sc, dw=acc,
-                                                              accumulate=True, pending=batch),
-                                 lambda: _C.conv_wgrad(xin, gout, shape, st, pd, out_scale=sc, pending=batch),
-                                 xin, gout)
-
-        if n3:
-            dw3 = wgrad(w3, y2, S3, 1, 0, s3)
-        S2 = _C.conv_forward(S3, _C.conv_weight_transpose(w3, s3), relu_mode=2, mask_ref=y2)
+        b = _BlockBackward(ctx.needs_input_grad[:5], x, w1, wd, s1, sd, stride)
+        S2, dw3 = b.open(G, out, out_private, y2, w2, w3, s3)
+        dw2 = dwo = dbo = None
         w2_1x1 = _as_1x1(w2)
         if n2:
             # [Cout][kh][kw][Cin] IS the 1x1 weight [Cout][K = (tap, ci)]: the gradient lands in w2's own layout
-            dw2 = wgrad(w2, cols, S2, 1, 0, s2, shape=(cout2, kh * kw * cin2, 1, 1))
+            dw2 = b.wgrad(w2, cols, S2, 1, 0, s2, shape=(cout2, kh * kw * cin2, 1, 1))
         gcols = _C.conv_forward(S2, _C.conv_weight_transpose(w2_1x1, s2))
         gy1, gom = _C.deform_sample_backward_om(y1, om, gcols, kh, kw, 1, kh // 2, 1, dg, modulated)
         if n_off:
             # gom's rows are padded to a multiple of four channels; the weight gradient keeps the parameter's own shape
             # (conv_wgrad reads the padded rows, dadet_conv_wgrad_partials_ld) and lands in its gradient buffer like every
-            # other weight of the block
-            dwo = wgrad(w_off, y1, gom, 1, kh // 2, None)
+            # other weight of the block — but not through the grouped launch, which takes dense rows only
+            dwo = b.wgrad(w_off, y1, gom, 1, kh // 2, None, grouped=False)
         if n_boff:
             dbo = streams.bias_grad(ctx.b_off, gom, cols=n_offch)
         # d y1 = [y1 > 0] * (sampled path + offset-conv path); the transposed weights carry zero columns for the padding
         S1 = _C.conv_forward(gom, _C.conv_weight_transpose(w_off, cout_pad=n_offpad), pad=kh // 2, addend=gy1, out=gy1,
                              relu_mode=2, mask_ref=y1)
-        if n1:
-            dw1 = wgrad(w1, x, S1, stride, 0, s1)
-        if nd and wd is not None:
-            dwd = wgrad(wd, x, S3, stride, 0, sd)
-        group.issue()
-        lane.reduce_batch(batch)
-        if need_x:
-            gate = dict(relu_mode=2, mask_ref=x) if in_relu else {}
-            hw = tuple(x.shape[2:])
-            if wd is None:
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=S3, **gate)
-            elif stride == 1:
-                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd))
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t, **gate)
-            else:
-                t = _C.conv_forward(S3, _C.conv_weight_transpose(wd, sd), out_spatial_stride=stride, out_hw=hw)
-                dx = _C.conv_forward(S1, _C.conv_weight_transpose(w1, s1), addend=t, out=t,
-                                     out_spatial_stride=stride, out_hw=hw, **gate)
-        lane.join()
+        dx, dw1, dwd = b.close(S1, in_relu)
         if dw2 is not None:     # returned to autograd (no persistent gradient buffer): back in w2's logical shape
             dw2 = torch.as_strided(dw2, (cout2, cin2, kh, kw), (kh * kw * cin2, 1, kw * cin2, cin2))
         return (dx, dw1, dw2, dw3, dwd, dwo, dbo) + (None,) * 13

@@ -72,7 +72,7 @@ class _DAInsHead(Function):
       forward : h1 = relu(fc1 x)                                   ONE GEMM for all passes
                 h1s = [h1 * m1_a ; h1 * m1_b]                      one launch
                 h2 = relu(fc2 h1s) * [m2_a ; m2_b]                 ONE GEMM over the stacked rows (+ the mask multiply)
-                fc3 + BCE sum + consistency sum                    one launch (csrc/da_heads.hip da_ins_fwd_kernel)
+                fc3 + BCE sum + consistency sum                    one launch (csrc/da_heads.hip da_ins_fwd_n_kernel)
       backward: tail (d fc2-preactivation, d fc3, d means)         one launch
                 fc2 weight / bias / data gradients                 GEMMs over the stacked rows
                 merge of the passes, ReLU gate, BOTH reversal weights   one launch (da_ins_merge_kernel)
@@ -80,7 +80,7 @@ class _DAInsHead(Function):
     `kinds`: ("bce",), ("cst",) or ("bce", "cst") — pass order = row order = order of the dropout draws."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, w3, b3, labels, means, masks1, masks2, grl, kinds, n_src, row_end=None):
+    def forward(ctx, x, w1, b1, w2, b2, w3, b3, labels, means, masks1, masks2, grl, kinds, row_end):
         R = x.shape[0]
         P = len(kinds)
         r_bce = R if "bce" in kinds else 0
@@ -93,13 +93,10 @@ class _DAInsHead(Function):
         h2.mul_(masks2.view(P * R, C2))
         w3v = w3.reshape(-1).contiguous()
         labels_f = labels.to(torch.float32) if r_bce else None
-        if row_end is None:         # two images, [source, target]: the kernels that take n_src
-            logits, sums = _C.da_ins_tail_forward(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, n_src)
-        else:
-            row_end = tuple(row_end) if r_cst else (0,) * len(row_end)
-            logits, sums = _C.da_ins_tail_forward_n(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, row_end)
+        row_end = tuple(row_end) if r_cst else (0,) * len(row_end)
+        logits, sums = _C.da_ins_tail_forward_n(h2, w3v, b3, labels_f, means if r_cst else None, r_bce, r_cst, row_end)
         ctx.save_for_backward(x, w1, w2, w3v, h1, h1s, masks1, h2, logits, labels_f, means if r_cst else None, grl)
-        ctx.conf = (R, P, r_bce, r_cst, n_src, tuple(w3.shape), row_end)
+        ctx.conf = (R, P, r_bce, r_cst, tuple(w3.shape), row_end)
         ctx.biases = (b1, b2)
         levels = int(means.shape[0]) if r_cst else 1
         bce = sums[0] / float(max(r_bce, 1))
@@ -112,19 +109,15 @@ class _DAInsHead(Function):
     @once_differentiable
     def backward(ctx, g_bce, g_cst, _g_logits):
         x, w1, w2, w3v, h1, h1s, masks1, h2, logits, labels_f, means, grl = ctx.saved_tensors
-        R, P, r_bce, r_cst, n_src, w3_shape, row_end = ctx.conf
+        R, P, r_bce, r_cst, w3_shape, row_end = ctx.conf
         need_x = ctx.needs_input_grad[0]
         C0, C1, C2 = x.shape[1], w1.shape[0], w2.shape[0]
         levels = int(means.shape[0]) if means is not None else 1
         coef = torch.stack([g_bce.reshape(()) / float(max(r_bce, 1)),
                             g_cst.reshape(()) / float(max(r_cst, 1) * levels)]).contiguous()
         # every mask value is 0 or 1 / keep, and a hidden unit that survived (h2 != 0) has mask 1 / keep
-        if row_end is None:
-            g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward(h2, w3v, logits, labels_f, means, coef,
-                                                                INS_DROPOUT_INV_KEEP, r_bce, r_cst, n_src)
-        else:
-            g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward_n(h2, w3v, logits, labels_f, means, coef,
-                                                                  INS_DROPOUT_INV_KEEP, r_bce, r_cst, row_end)
+        g_z2, g_w3, g_b3, g_means = _C.da_ins_tail_backward_n(h2, w3v, logits, labels_f, means, coef,
+                                                              INS_DROPOUT_INV_KEEP, r_bce, r_cst, row_end)
         g_z2 = g_z2.view(P * R, C2, 1, 1)
         g_w2 = _C.conv_wgrad(h1s.view(P * R, C1, 1, 1), g_z2, (C2, C1, 1, 1), 1, 0).view(C2, C1)
         g_b2 = bias_grad(ctx.biases[1], g_z2)
@@ -136,7 +129,7 @@ class _DAInsHead(Function):
         g_x = None
         if need_x:
             g_x = _C.conv_forward(g1_x.view(R, C1, 1, 1), _C.conv_weight_transpose(w1.view(C1, C0, 1, 1))).view(R, C0)
-        return (g_x, g_w1, g_b1, g_w2, g_b2, g_w3.view(w3_shape), g_b3, None, g_means) + (None,) * 6
+        return (g_x, g_w1, g_b1, g_w2, g_b2, g_w3.view(w3_shape), g_b3, None, g_means) + (None,) * 5
 
 
 INS_DROPOUT_P = 0.5                                   # DAInsHead: F.dropout(p=0.5) after fc1 and fc2 (da_heads.py:63,65)
@@ -149,17 +142,16 @@ def da_instance_head(x, head, labels, means, masks1, masks2, grl, kinds, n_src, 
     float [P] device tensor of the passes' gradient-reversal weights; rows_per_image: host ints, how many of the R rows
     (stacked in image order) belong to each image — without it N = 2 and the first n_src rows are the source image's
     -> (mean BCE, consistency loss, logits [P, R])"""
-    row_end = None
+    R = x.shape[0]
+    row_end = _C.two_image_ends(R, n_src)
     if rows_per_image is not None:
         rows_per_image = [int(r) for r in rows_per_image]
-        if sum(rows_per_image) != x.shape[0] or (means is not None and means.shape[1] != len(rows_per_image)):
+        if sum(rows_per_image) != R or (means is not None and means.shape[1] != len(rows_per_image)):
             raise ValueError("instance head: rows_per_image {} does not describe {} rows of {} images".format(
-                rows_per_image, x.shape[0], "?" if means is None else means.shape[1]))
-        if len(rows_per_image) != 2 or rows_per_image[0] != int(n_src):
-            row_end = tuple(sum(rows_per_image[:i + 1]) for i in range(len(rows_per_image)))
+                rows_per_image, R, "?" if means is None else means.shape[1]))
+        row_end = tuple(sum(rows_per_image[:i + 1]) for i in range(len(rows_per_image)))
     return _DAInsHead.apply(x, head.fc1_da.weight, head.fc1_da.bias, head.fc2_da.weight, head.fc2_da.bias,
-                            head.fc3_da.weight, head.fc3_da.bias, labels, means, masks1, masks2, grl, tuple(kinds),
-                            int(n_src), row_end)
+                            head.fc3_da.weight, head.fc3_da.bias, labels, means, masks1, masks2, grl, tuple(kinds), row_end)
 
 
 class _TripletW(Function):

@@ -741,6 +741,8 @@ int dadet_da_img_head_loss_backward_gm(const float* t, const float* w2, const fl
  *             (caller zero-fills sums; means [levels][2] = per-level mean sigmoid of the image head on image 0 / 1)
  *   backward: coef[0] / coef[1] (device) = d loss / d sums[0] / d sums[1];  g_z = gradient w.r.t. fc2's PRE-activation
  *             (dropout scale inv_keep and ReLU gate folded in); g_w3 / g_b3 / g_means are accumulated (caller zero-fills).
+ * These two entries are the `_n` entries below with num_images = 2 and row_end = {n_src clamped to 0 .. R_cst, R_cst}: an
+ * n_src above R_cst gives every consistency row to image 0, a negative one to image 1.
  * dadet_da_ins_dropout_rows: out[p][r] = h1[r] * masks[p][r] (the passes share the first layer up to its dropout mask).
  * dadet_da_ins_merge: backward through that shared layer — g_w = [h1 > 0] * sum_p masks[p] * g[p] (parameter gradients),
  *   g_x = [h1 > 0] * sum_p grl[p] * masks[p] * g[p] (towards the ROI features: the passes' gradient-reversal weights,
@@ -756,8 +758,7 @@ int dadet_da_ins_tail_backward(const float* h, const float* w3, const float* log
  * array, copied into the launch's arguments: no device buffer, no synchronisation) holds the ascending ends of the images'
  * row segments, row_end[num_images - 1] == R_cst; an image may own no row.  means / g_means are [levels][num_images], and
  * consistency row j of image i adds sum_l |means[l][i] - sigmoid(logit_j)|.  The backward keeps levels * num_images <= 512
- * sums in LDS.  Bad arguments are refused before anything is written.  num_images = 2 with row_end = {n_src, R_cst} gives the
- * forward bits of dadet_da_ins_tail_forward. */
+ * sums in LDS.  Bad arguments are refused before anything is written. */
 int dadet_da_ins_tail_forward_n(const float* h, const float* w3, const float* b3, const float* labels,
                                 const float* means, float* logits, float* sums, int R_bce, int R_cst,
                                 const int* row_end, int num_images, int levels, int C, void* stream);

@@ -5,14 +5,17 @@ Bars, gates and the seed search are those of tests/test_da_heads_gpu.py (its mod
 the instance tail is that file's `_ins_reference` with the consistency rows of ANY number of images: row j of image i is
 compared with means[l][i], and the bound of g_means[l][i] is a sum over image i's rows."""
 import ctypes
+import hashlib
+import json
 import math
+import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from test_da_heads_gpu import (CL, EPS32, FLOOR, GATE, INV_KEEP, U, _assert_gate_margin, _check, _five_times, _ins_inputs,
-                               _spread, _sum_bound, _triplet_reference, f32)
+from test_da_heads_gpu import (CL, EPS32, FLOOR, GATE, INV_KEEP, U, _assert_gate_margin, _check, _five_times,
+                               _ins_conditions, _ins_inputs, _ins_reference, _spread, _sum_bound, _triplet_reference, f32)
 
 pytestmark = pytest.mark.gpu
 
@@ -150,17 +153,80 @@ def test_ins_tail_n_against_float64(device, C, rows, Rb, L):
     assert not bool(g_means.cpu()[:, empty].any())               # an image without rows: exactly no gradient
 
 
+# the two-image cases whose forward bits tests/golden/da_ins_tail_bits.json holds: name -> (seed, C, R_bce, R_cst, n_src, L)
+INS_BITS_CASES = {
+    "two_images": (312, 12, 7, 7, 3, 3),
+    "n_src_0": (313, 12, 7, 7, 0, 3),                 # every consistency row is image 1's
+    "n_src_all": (314, 12, 7, 7, 7, 3),               # every consistency row is image 0's
+    "no_consistency_rows": (315, 12, 7, 0, 0, 3),     # means is None
+    "no_bce_rows": (316, 12, 0, 7, 3, 3),             # labels is None
+    "production_rows": (317, 1024, 512, 512, 256, 1),
+}
+# n_src outside 0 .. R_cst: name -> (the case it is run on, the n_src it is run with, the case whose bits it gives)
+INS_BITS_OUTSIDE = {"n_src_above": ("n_src_all", 7 + 5, "n_src_all"), "n_src_negative": ("n_src_0", -2, "n_src_0")}
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def ins_bits(case, device, run):
+    """-> {"logits": sha256, "sums": sha256} of run(h, w3, b3, labels, means, R_bce, R_cst, n_src) on the case's inputs"""
+    seed, C, Rb, Rc, n_src, L = INS_BITS_CASES[case]
+    _, _, h, w3, b3, labels, means = _ins_inputs(seed, C, Rb, Rc, n_src, L)
+    dev = lambda v: v.to(device) if v is not None else None      # noqa: E731
+    logits, sums = run(dev(h), dev(w3), dev(b3), dev(labels), dev(means), Rb, Rc, n_src)
+    return {"logits": _sha(logits), "sums": _sha(sums)}
+
+
+def _two_image_entries(device):
+    """-> (forward, backward) with the arguments of `_C.da_ins_tail_forward` / `_backward`, calling the native two-image
+    entries dadet_da_ins_tail_forward / _backward themselves, n_src as given: `_C` calls only the `_n` entries, and gives
+    the two-image wrappers their ends through its own `two_image_ends`"""
+    from da_detect_amd import _C, _lib
+    p, st = _C._p, _C._stream()
+
+    def forward(h, w3, b3, labels, means, Rb, Rc, n_src):
+        logits, sums = torch.empty(Rb + Rc, device=device), torch.zeros(2, device=device)
+        _lib.call("dadet_da_ins_tail_forward", p(h), p(w3), p(b3), p(labels), p(means), p(logits), p(sums), Rb, Rc, n_src,
+                  means.shape[0] if means is not None else 0, h.shape[1], st)
+        return logits, sums
+
+    def backward(h, w3, logits, labels, means, coef, inv_keep, Rb, Rc, n_src):
+        C, L = h.shape[1], means.shape[0] if means is not None else 0
+        g_z, g_w3, g_b3 = torch.empty_like(h), torch.zeros(C, device=device), torch.zeros(1, device=device)
+        g_means = torch.zeros(L, 2, device=device) if L else None
+        _lib.call("dadet_da_ins_tail_backward", p(h), p(w3), p(logits), p(labels), p(means), p(coef), inv_keep, p(g_z),
+                  p(g_w3), p(g_b3), p(g_means), Rb, Rc, n_src, L, C, st)
+        return g_z, g_w3, g_b3, g_means
+
+    return forward, backward
+
+
 def test_ins_tail_n_two_images_gives_the_old_entry_bits(device):
-    """rows [3, 4] through the `_n` entry: logits and both sums equal dadet_da_ins_tail_forward's bit for bit (same grid,
-    same order of every sum); its backward meets the same reference"""
+    """The two-image entries' kernels are gone: dadet_da_ins_tail_forward builds the table {clamp(n_src, 0, R_cst), R_cst}
+    and launches the kernel of the `_n` entry.  What they wrote is kept as bits: the SHA-256 of logits and of both sums that
+    the two-image entry gave at the last commit where it had kernels of its own, on an MI355X, twice
+    (tests/golden/da_ins_tail_bits.json).  The native two-image entry, called directly, the two-image wrapper and the `_n`
+    wrapper with [n_src, R_cst] all give them — same grid, same order of every sum — and an n_src above R_cst / below 0
+    gives what R_cst / 0 gives, through the native entry's clamp and through the wrapper's."""
     from da_detect_amd import _C
 
-    C, Rb, Rc, n_src, L = 12, 7, 7, 3, 3
-    z, mask, h, w3, b3, labels, means = _ins_inputs(312, C, Rb, Rc, n_src, L)
-    hd, wd, bd, ld, md = (v.to(device) for v in (h, w3, b3, labels, means))
-    old = _C.da_ins_tail_forward(hd, wd, bd, ld, md, Rb, Rc, n_src)
-    new = _C.da_ins_tail_forward_n(hd, wd, bd, ld, md, Rb, Rc, [n_src, Rc])
-    assert torch.equal(old[0], new[0]) and torch.equal(old[1], new[1])
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "da_ins_tail_bits.json")) as f:
+        recorded = json.load(f)
+    assert sorted(recorded["hashes"]) == sorted(INS_BITS_CASES) and recorded["not_reproducible"] == []
+    native_forward, _ = _two_image_entries(device)
+    for case in INS_BITS_CASES:
+        assert ins_bits(case, device, native_forward) == recorded["hashes"][case], case
+        assert ins_bits(case, device, _C.da_ins_tail_forward) == recorded["hashes"][case], case
+        assert ins_bits(case, device, lambda *a: _C.da_ins_tail_forward_n(*a[:-1], [a[-1], a[-2]])) \
+            == recorded["hashes"][case], case
+    for on, n_src, gives in INS_BITS_OUTSIDE.values():
+        for run in (native_forward, _C.da_ins_tail_forward):
+            assert ins_bits(on, device, lambda *a: run(*a[:-1], n_src)) == recorded["hashes"][gives], n_src
+    _, C, Rb, Rc, n_src, L = INS_BITS_CASES["two_images"]
+    _, _, h, w3, b3, labels, means = _ins_inputs(312, C, Rb, Rc, n_src, L)
+    new = _C.da_ins_tail_forward_n(*(v.to(device) for v in (h, w3, b3, labels, means)), Rb, Rc, [n_src, Rc])
     assert float(new[1][1]) > 0.0
     # thousands of rows, magnitudes over six decades: the workgroups' partial sums are added in one order
     g = torch.Generator().manual_seed(72)
@@ -172,6 +238,37 @@ def test_ins_tail_n_two_images_gives_the_old_entry_bits(device):
     means = torch.rand(2, 4, generator=g).to(device)
     b3 = torch.tensor([0.05], device=device)
     _five_times(lambda: _C.da_ins_tail_forward_n(hs, w3, b3, labels, means, Rb, Rc, _ends(rows)))
+
+
+@pytest.mark.parametrize("n_src", [3, 7 + 5, -2], ids=lambda v: "n_src=" + str(v))
+def test_ins_tail_two_image_entries_against_float64(device, n_src):
+    """dadet_da_ins_tail_forward / _backward called directly, C = 12 and 7 + 7 rows, with n_src inside, above and below
+    0 .. R_cst: the float64 reference and bounds of test_da_heads_gpu.test_ins_tail_against_float64, whose row image is
+    (row >= n_src) for ANY n_src — no clamp on the reference's side"""
+    C, Rb, Rc, L = 12, 7, 7, 3
+    for seed in range(300 + C, 300 + C + 64):
+        z, mask, h, w3, b3, labels, means = _ins_inputs(seed, C, Rb, Rc, n_src, L)
+        if _ins_conditions(h, w3, b3, means, Rb, Rc, n_src, False):
+            break
+    else:
+        raise AssertionError("no seed gives a reference clear of the switching points")
+    _assert_gate_margin(h.double())
+    forward, backward = _two_image_entries(device)
+    hd, wd, bd, ld, md = (v.to(device) for v in (h, w3, b3, labels, means))
+    logits, sums = forward(hd, wd, bd, ld, md, Rb, Rc, n_src)
+    h64 = h.double()
+    _check("logits", logits, h64 @ w3.double() + b3.double(),
+           (C + 2) * U * (h64.abs() @ w3.double().abs() + b3.double().abs()))
+    coef = torch.tensor([0.7 / Rb, -1.3 / (Rc * L)])
+    ref = _ins_reference(z, mask, h, w3, b3, labels, means, logits.double().cpu(), coef, Rb, Rc, n_src)
+    _check("BCE sum", sums[0], *ref["BCE sum"])
+    _check("consistency sum", sums[1], *ref["consistency sum"])
+    g_z, g_w3, g_b3, g_means = backward(hd, wd, logits, ld, md, coef.to(device), INV_KEEP, Rb, Rc, n_src)
+    for name, g in (("g_z", g_z), ("g_w3", g_w3), ("g_b3", g_b3), ("g_means", g_means)):
+        _check(name, g, *ref[name])
+    assert bool((g_z.cpu()[h == 0] == 0).all())
+    if not 0 < n_src < Rc:
+        assert not bool(g_means.cpu()[:, 0 if n_src <= 0 else 1].any())      # the image without rows: exactly no gradient
 
 
 def test_ins_tail_n_refusals_write_nothing(device):

@@ -279,14 +279,14 @@ def _frozen_and_unfrozen(device):
     return _CACHE["pair"]
 
 
-# parameters whose gradient da_img_bwd_kernel / da_ins_bwd_kernel (csrc/da_heads.hip) sum with float atomics
+# parameters whose gradient da_img_bwd_kernel / da_ins_bwd_n_kernel (csrc/da_heads.hip) sum with float atomics
 _ATOMIC_GRADS = ("da_heads.imghead.conv2_da.weight", "da_heads.imghead.conv2_da.bias",
                  "da_heads.inshead.fc3_da.weight", "da_heads.inshead.fc3_da.bias")
 
 
 def test_unfreezing_changes_no_loss(device):
     """FREEZE_CONV_BODY_AT 2 against 0 from one state dict: the loss dicts are bit-identical.  (The three DA losses are
-    part of this since da_img_fwd_kernel and da_ins_fwd_kernel add their partial sums in a fixed order: with float atomics
+    part of this since da_img_fwd_kernel and da_ins_fwd_n_kernel add their partial sums in a fixed order: with float atomics
     they differed in the last bits between two runs of ONE model — 1.03337121 / 1.03337097, 1.26122475 / 1.26122487,
     0.340123802 / 0.340123713 at level 2 — and so between the levels.)"""
     _, _, _, _, losses2, losses0 = _frozen_and_unfrozen(device)
@@ -304,7 +304,7 @@ def test_unfreezing_adds_gradients_and_changes_none(device):
 
     Four tensors are not bit-identical, between the levels as between two runs of one level (measured: 6e-8 .. 1.7e-7
     relative L2 in both pairings): the last layers of the two DA heads, whose gradients da_img_bwd_kernel and
-    da_ins_bwd_kernel (csrc/da_heads.hip) add with float atomics in arrival order.  They are held to 1e-6 relative L2.
+    da_ins_bwd_n_kernel (csrc/da_heads.hip) add with float atomics in arrival order.  They are held to 1e-6 relative L2.
     The loss dicts: test_unfreezing_changes_no_loss."""
     from da_detect_amd.solver import make_optimizer
 

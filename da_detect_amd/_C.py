@@ -310,6 +310,55 @@ def coco_match(det_box, gt_box, gt_area, gt_crowd, det_off, gt_off, iou_thr, are
     return matched, ignored, npig
 
 
+VOC_MATCH_MAX_THRESHOLDS = 16    # IoU thresholds per launch (csrc/voc_match.hip)
+
+
+def voc_match_workspace_bytes(det_off, gt_off, n_det, n_gt, n_thr):
+    """scratch of voc_match for these offset tables; validates them on the host exactly as the launch does (no device)"""
+    d_host, nd = _int_table(det_off)
+    g_host, ng = _int_table(gt_off)
+    if nd != ng or nd < 1:
+        raise _lib.DadetError("voc_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_voc_match_workspace_bytes", d_host, g_host, nd - 1, int(n_det), int(n_gt), int(n_thr), ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def voc_match(det_box, gt_box, gt_difficult, det_off, gt_off, iou_thr):
+    """PASCAL VOC box matching of every (image, class) pair in one launch (dadet_voc_match): det_box [Nd, 4] / gt_box [Ng, 4]
+    xyxy float32, gt_difficult [Ng] uint8 on the device; det_off / gt_off host ints [P + 1] (pair p's slices; detections best
+    first, any number); iou_thr [T <= VOC_MATCH_MAX_THRESHOLDS] host floats ->
+    (match int8 [T, Nd] in {-1, 0, 1}, n_pos int32 [P], gt_index int32 [Nd], iou_max float32 [Nd]) on the device."""
+    for t, name, dtype in ((det_box, "det_box", torch.float32), (gt_box, "gt_box", torch.float32),
+                           (gt_difficult, "gt_difficult", torch.uint8)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.DadetError(
+                "%s must be a tensor on the HIP device: the da_detect_amd operators have no CPU path" % name)
+        if t.dtype != dtype:
+            raise _lib.DadetError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    det_box, gt_box, gt_difficult = det_box.contiguous(), gt_box.contiguous(), gt_difficult.contiguous()
+    n_det, n_gt = int(det_box.shape[0]), int(gt_box.shape[0])
+    if det_box.numel() != 4 * n_det or gt_box.numel() != 4 * n_gt or gt_difficult.numel() != n_gt:
+        raise _lib.DadetError("voc_match: boxes must be [n, 4], gt_difficult [n_gt]")
+    d_host, nd = _int_table(det_off)
+    g_host, ng = _int_table(gt_off)
+    if nd != ng or nd < 1:
+        raise _lib.DadetError("voc_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
+    pairs = nd - 1
+    thr_host, T = _f64_table(iou_thr)
+    dev = det_box.device
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_voc_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T, ctypes.byref(nbytes))
+    ws = _workspace(nbytes.value, dev)
+    match = torch.empty((T, n_det), dtype=torch.int8, device=dev)
+    n_pos = torch.empty(pairs, dtype=torch.int32, device=dev)
+    gt_index = torch.empty(n_det, dtype=torch.int32, device=dev)
+    iou_max = torch.empty(n_det, dtype=torch.float32, device=dev)
+    _lib.call("dadet_voc_match", _p(det_box), _p(gt_box), _p(gt_difficult), d_host, g_host, pairs, n_det, n_gt, thr_host, T,
+              _p(ws), ctypes.c_size_t(ws.numel()), _p(match), _p(n_pos), _p(gt_index), _p(iou_max), _stream())
+    return match, n_pos, gt_index, iou_max
+
+
 def nms(dets, scores, threshold):
     """_C.nms(dets[N,4], scores[N], thr) -> int64[K] kept original indices, ascending (nms.h:10-28)."""
     if dets.numel() == 0:

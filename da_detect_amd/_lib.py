@@ -85,6 +85,9 @@ _SIGNATURES = {
     "dadet_coco_match_workspace_bytes": [POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)],
     "dadet_coco_match": [_P, _P, _P, _P, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(ctypes.c_double), c_int,
                          POINTER(ctypes.c_double), c_int, _P, c_size_t, _P, _P, _P, _P],
+    "dadet_voc_match_workspace_bytes": [POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_size_t)],
+    "dadet_voc_match": [_P, _P, _P, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(ctypes.c_double), c_int, _P,
+                        c_size_t, _P, _P, _P, _P, _P],
     "dadet_roi_align_forward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],

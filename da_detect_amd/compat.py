@@ -36,6 +36,8 @@ _RELOCATED = {
     "data.datasets.evaluation": "data.evaluation",
     "data.datasets.evaluation.coco": "data.evaluation.coco",
     "data.datasets.evaluation.coco.coco_eval": "data.evaluation.coco.coco_eval",
+    "data.datasets.evaluation.voc": "data.evaluation.voc",
+    "data.datasets.evaluation.voc.voc_eval": "data.evaluation.voc.voc_eval",
 }
 
 

@@ -49,12 +49,26 @@ class DatasetCatalog(object):
         "bdd100k_daytime_clear_city_street_val_cocostyle": {
             "img_dir": "bdd100k/daytime_clear_city_street_coco/val",
             "ann_file": "bdd100k/daytime_clear_city_street_coco/val_bdd100k_coco.json"},
+        "voc_2007_train": {"data_dir": "voc/VOC2007", "split": "train"},
+        "voc_2007_val": {"data_dir": "voc/VOC2007", "split": "val"},
+        "voc_2007_test": {"data_dir": "voc/VOC2007", "split": "test"},
+        "voc_2012_train": {"data_dir": "voc/VOC2012", "split": "train"},
+        "voc_2012_val": {"data_dir": "voc/VOC2012", "split": "val"},
+        "voc_2012_test": {"data_dir": "voc/VOC2012", "split": "test"},
     }
 
     @classmethod
     def register(cls, name, img_dir, ann_file):
         """add / replace a COCO-style entry (absolute paths are kept, relative ones resolve under DATA_DIR)"""
         cls.DATASETS[name] = {"img_dir": img_dir, "ann_file": ann_file}
+
+    @classmethod
+    def register_voc(cls, name, data_dir, split):
+        """add / replace an entry in PASCAL VOC layout (Annotations, ImageSets/Main/<split>.txt, JPEGImages under `data_dir`);
+        the name must contain "voc" and must not contain "coco": `get` dispatches on the name, as the reference does"""
+        if "voc" not in name or "coco" in name:
+            raise ValueError('a VOC-layout dataset name must contain "voc" and not "coco", got {!r}'.format(name))
+        cls.DATASETS[name] = {"data_dir": data_dir, "split": split}
 
     @staticmethod
     def get(name):
@@ -65,6 +79,13 @@ class DatasetCatalog(object):
             data_dir = os.environ.get("DADET_DATA_DIR", DatasetCatalog.DATA_DIR)     # the environment wins, at call time
             return dict(factory="COCODataset", args=dict(root=os.path.join(data_dir, attrs["img_dir"]),
                                                          ann_file=os.path.join(data_dir, attrs["ann_file"])))
+        if "voc" in name:
+            if name not in DatasetCatalog.DATASETS:
+                raise RuntimeError("Dataset not available: {}".format(name))
+            attrs = DatasetCatalog.DATASETS[name]
+            data_dir = os.environ.get("DADET_DATA_DIR", DatasetCatalog.DATA_DIR)
+            return dict(factory="PascalVOCDataset", args=dict(data_dir=os.path.join(data_dir, attrs["data_dir"]),
+                                                              split=attrs["split"]))
         raise RuntimeError("Dataset not available: {}".format(name))
 
 

@@ -88,6 +88,8 @@ def _from_catalog(name, catalog, transforms, is_train, is_source):
     args = dict(data["args"])
     if data["factory"] == "COCODataset":
         args["remove_images_without_annotations"] = is_train
+    if data["factory"] == "PascalVOCDataset":
+        args["use_difficult"] = not is_train
     args["transforms"] = transforms
     args["is_source"] = is_source
     return factory(**args)
@@ -192,15 +194,23 @@ def make_test_data_loader(cfg, dataset, is_distributed=False):
     return _loader_for(cfg, dataset, images_per_gpu(cfg, False), bool(is_distributed), is_distributed, None, 0, collator)
 
 
+def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True):
+    """spec = (ann_file, image_root) for a COCO-style dataset, or ("voc:" + data_dir, split) for one in PASCAL VOC layout
+    (the command-line form `voc:DIR,SPLIT` of the tools); the train / test switches are those of `_from_catalog`"""
+    first, second = spec
+    if first.startswith("voc:"):
+        return D.PascalVOCDataset(first[len("voc:"):], second, use_difficult=not is_train, transforms=transforms,
+                                  is_source=is_source)
+    return COCODataset(first, second, remove_images_without_annotations=is_train, transforms=transforms, is_source=is_source)
+
+
 def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0):
-    """dataset_specs = {"source": (ann_file, root), "target": (...)[, "auxiliary": (...)]} -> one loader per domain,
-    iterated jointly by do_da_train (each carrying IMS_PER_BATCH // (2 * num_gpus) images per step)"""
+    """dataset_specs = {"source": (ann_file, root), "target": (...)[, "auxiliary": (...)]} (or `dataset_from_spec`'s VOC form)
+    -> one loader per domain, iterated jointly by do_da_train (each carrying IMS_PER_BATCH // (2 * num_gpus) images per step)"""
     tf = build_transforms(cfg, True)
     out = []
     for name in [n for n in ("source", "target", "auxiliary") if n in dataset_specs]:
-        ann, root = dataset_specs[name]
-        ds = COCODataset(ann, root, remove_images_without_annotations=True, transforms=tf,
-                         is_source=(name == "source"))
+        ds = dataset_from_spec(dataset_specs[name], tf, True, name == "source")
         out.append(_train_loader(cfg, ds, is_distributed, start_iter, BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)))
     return out
 
@@ -208,7 +218,6 @@ def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0)
 def make_triplet_data_loader(cfg, dataset_specs, is_distributed=False, start_iter=0):
     """one loader over index-aligned (source, target, auxiliary) samples (build.py:23-63, 332-419)"""
     tf = build_transforms(cfg, True)
-    ds = [COCODataset(*dataset_specs[n], remove_images_without_annotations=True, transforms=tf,
-                      is_source=(n == "source")) for n in ("source", "target", "auxiliary")]
+    ds = [dataset_from_spec(dataset_specs[n], tf, True, n == "source") for n in ("source", "target", "auxiliary")]
     return _train_loader(cfg, TripletDataset(ds), is_distributed, start_iter,
                          BatchCollator_triplet(cfg.DATALOADER.SIZE_DIVISIBILITY))

@@ -1,10 +1,11 @@
-"""COCO-style detection datasets with a domain flag (reference: maskrcnn_benchmark/data/datasets/coco.py:44-124 and
-data/build.py:23-63 `Dataset_triplet`).  The annotation file is read with the json module (pycocotools /
+"""COCO-style and PASCAL VOC detection datasets with a domain flag (reference: maskrcnn_benchmark/data/datasets/coco.py:44-124,
+data/datasets/voc.py and data/build.py:23-63 `Dataset_triplet`).  The annotation file is read with the json module (pycocotools /
 torchvision.datasets.CocoDetection are not needed for bounding boxes); segmentation masks and keypoints are outside the
 DA Faster R-CNN path."""
 import copy
 import json
 import os
+import xml.etree.ElementTree as ET
 
 import numpy as np
 import torch
@@ -37,6 +38,7 @@ class COCODataset(torch.utils.data.Dataset):
         if remove_images_without_annotations:
             self.ids = [i for i in self.ids if has_valid_annotation(self.anns_of.get(i, []))]
         cat_ids = sorted(c["id"] for c in data.get("categories", []))
+        self.category_names = {c["id"]: c.get("name", str(c["id"])) for c in data.get("categories", [])}
         self.json_category_id_to_contiguous_id = {v: i + 1 for i, v in enumerate(cat_ids)}
         self.contiguous_category_id_to_json_id = {v: k for k, v in self.json_category_id_to_contiguous_id.items()}
         self.id_to_img_map = {k: v for k, v in enumerate(self.ids)}
@@ -71,6 +73,107 @@ class COCODataset(torch.utils.data.Dataset):
 
     def get_img_info(self, index):
         return self.imgs[self.id_to_img_map[index]]
+
+    def get_groundtruth(self, index):
+        """every annotation of the image as the VOC scorer wants it (data/evaluation/voc): xyxy boxes with `labels` and
+        `difficult` = iscrowd (VOC's "neither right nor wrong to find" is what COCO means by a crowd region)"""
+        info = self.get_img_info(index)
+        anno = self.anns_of.get(self.id_to_img_map[index], [])
+        boxes = torch.as_tensor([o["bbox"] for o in anno], dtype=torch.float32).reshape(-1, 4)
+        target = BoxList(boxes, (info["width"], info["height"]), mode="xywh").convert("xyxy")
+        target.add_field("labels", torch.tensor([self.json_category_id_to_contiguous_id[o["category_id"]] for o in anno],
+                                                dtype=torch.int64))
+        target.add_field("difficult", torch.tensor([bool(o.get("iscrowd", 0)) for o in anno], dtype=torch.bool))
+        return target
+
+    def map_class_id_to_class_name(self, class_id):
+        if class_id == 0:
+            return "__background__"
+        json_id = self.contiguous_category_id_to_json_id[class_id]
+        return self.category_names.get(json_id, str(json_id))
+
+
+class PascalVOCDataset(torch.utils.data.Dataset):
+    """a dataset in PASCAL VOC layout: Annotations/<id>.xml, ImageSets/Main/<split>.txt, JPEGImages/<id>.jpg.  `classes`
+    replaces the twenty VOC names (background first; Cityscapes in VOC layout has eight); `use_difficult` keeps the objects
+    marked difficult (evaluation needs them: they are neither hits nor misses), training drops them."""
+
+    CLASSES = ("__background__ ", "aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow",
+               "diningtable", "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
+
+    def __init__(self, data_dir, split, use_difficult=False, transforms=None, is_source=True, decode_to_tensor=False,
+                 classes=None):
+        self.root = data_dir
+        self.image_set = split
+        self.keep_difficult = use_difficult
+        self._transforms = transforms
+        self.is_source = is_source
+        self.decode_to_tensor = decode_to_tensor     # True: return uint8 [H,W,3] for data/device_prep.py
+        self._annopath = os.path.join(self.root, "Annotations", "%s.xml")
+        self._imgpath = os.path.join(self.root, "JPEGImages", "%s.jpg")
+        self._imgsetpath = os.path.join(self.root, "ImageSets", "Main", "%s.txt")
+        with open(self._imgsetpath % self.image_set) as f:
+            self.ids = [line.strip() for line in f if line.strip()]
+        self.id_to_img_map = dict(enumerate(self.ids))
+        if classes is not None:
+            self.CLASSES = tuple(classes)
+        self.class_to_ind = {name: i for i, name in enumerate(self.CLASSES)}
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __getitem__(self, index):
+        from PIL import Image
+
+        img = Image.open(self._imgpath % self.ids[index]).convert("RGB")
+        target = self.get_groundtruth(index)
+        labels = target.get_field("labels")
+        target.add_field("is_source", torch.full_like(labels, bool(self.is_source), dtype=torch.bool))
+        target = target.clip_to_image(remove_empty=True)
+        if self.decode_to_tensor:
+            return torch.from_numpy(np.array(img, dtype=np.uint8)), target, index
+        if self._transforms is not None:
+            img, target = self._transforms(img, target)
+        return img, target, index
+
+    def _root_of(self, index):
+        return ET.parse(self._annopath % self.ids[index]).getroot()
+
+    @staticmethod
+    def _size(anno):
+        size = anno.find("size")
+        return int(size.find("height").text), int(size.find("width").text)
+
+    def get_groundtruth(self, index):
+        anno = self._preprocess_annotation(self._root_of(index))
+        height, width = anno["im_info"]
+        target = BoxList(anno["boxes"], (width, height), mode="xyxy")
+        target.add_field("labels", anno["labels"])
+        target.add_field("difficult", anno["difficult"])
+        return target
+
+    def _preprocess_annotation(self, target):
+        """VOC pixel indices are 1-based: every coordinate loses 1"""
+        boxes, labels, difficult = [], [], []
+        for obj in target.iter("object"):
+            hard = obj.find("difficult")
+            hard = hard is not None and int(hard.text) == 1
+            if hard and not self.keep_difficult:
+                continue
+            bb = obj.find("bndbox")
+            boxes.append([int(bb.find(k).text) - 1 for k in ("xmin", "ymin", "xmax", "ymax")])
+            labels.append(self.class_to_ind[obj.find("name").text.lower().strip()])
+            difficult.append(hard)
+        return {"boxes": torch.tensor(boxes, dtype=torch.float32).reshape(-1, 4),
+                "labels": torch.tensor(labels, dtype=torch.int64), "difficult": torch.tensor(difficult, dtype=torch.bool),
+                "im_info": self._size(target)}
+
+    def get_img_info(self, index):
+        height, width = self._size(self._root_of(index))
+        return {"height": height, "width": width}
+
+    def map_class_id_to_class_name(self, class_id):
+        return self.CLASSES[class_id]
 
 
 class ConcatDataset(torch.utils.data.ConcatDataset):

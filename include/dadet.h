@@ -125,6 +125,31 @@ int dadet_coco_match(const double* det_box, const double* gt_box, const double* 
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PASCAL VOC box matching — the per-(image, class) matching of the reference's VOC scorer for a whole dataset in ONE launch
+ *   (data/datasets/evaluation/voc/voc_eval.py:108-134 `calc_detection_voc_prec_rec`).
+ * Pair p holds detections det_off_host[p] .. det_off_host[p+1] (any number, already in descending score) and ground truths
+ * gt_off_host[p] .. gt_off_host[p+1] (annotation order, any number).  det_box [n_det][4] and gt_box [n_gt][4] are xyxy
+ * float32, gt_difficult [n_gt] uint8.  iou_thr_host [1 <= n_thr <= 16] is a HOST array passed by value.
+ * IoU in float32, contraction off: x2 += 1, y2 += 1 on both boxes, then area = (x2 - x1 + 1) * (y2 - y1 + 1),
+ * wh = max(min(rb) - max(lt) + 1, 0), iou = inter / ((area_d + area_g) - inter) — bit-identical to a host float32 evaluation.
+ * gt_index = argmax over the pair's ground truths (first index on ties; independent of other detections), -1 without ground
+ * truth; iou_max the maximum (0 without ground truth).  Per threshold t: no candidate where (double)iou_max < thr[t]; match
+ * = -1 for a difficult candidate, 1 for the smallest detection index with that candidate, 0 otherwise (no candidate included).
+ * Outputs (device): match_out int8 [n_thr][n_det]; n_pos_out int32 [pairs] = non-difficult ground truths of the pair;
+ * gt_index_out int32 [n_det]; iou_max_out float32 [n_det].  The offset tables are validated on the host (start at 0, never
+ * decrease, end at n_det / n_gt) BEFORE anything is launched — DADET_EINVAL otherwise — and the validated copy is what the
+ * kernel reads (uploaded into the workspace; the call's one host wait).  One workgroup per pair; its ground truths (box,
+ * difficult byte, first claimant per threshold: G * (16 + 1 + 4 n_thr) bytes) live in LDS when they fit 160 KiB, else in the
+ * workspace, which must be 16-byte aligned; the query sizes it.  Integer atomicMin only: the result does not depend on timing.
+ * ----------------------------------------------------------------------------------------------*/
+int dadet_voc_match_workspace_bytes(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt, int n_thr,
+                                    size_t* bytes_out);
+int dadet_voc_match(const float* det_box, const float* gt_box, const unsigned char* gt_difficult, const int* det_off_host,
+                    const int* gt_off_host, int pairs, int n_det, int n_gt, const double* iou_thr_host, int n_thr,
+                    void* workspace, size_t workspace_bytes, signed char* match_out, int* n_pos_out, int* gt_index_out,
+                    float* iou_max_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ROIAlign — replaces `_C.roi_align_forward` / `_C.roi_align_backward`
  *   reference: csrc/ROIAlign.h:11-45, csrc/cpu/ROIAlign_cpu.cpp:114-257, csrc/cuda/ROIAlign_cuda.cu:65-254.
  * input  [B][H][W][C] NHWC, rois [R][5] = (batch_idx, x1, y1, x2, y2), output [R][PH][PW][C] NHWC.

@@ -16,7 +16,14 @@ dataset, `--ckpt`, `--output-dir` and KEY VALUE overrides, so the per-class tabl
 `--proposals`: the predictions are RPN proposals with an `objectness` field; AR at 100 and 1000 proposals for four area
 ranges is logged and `box_proposals.pth` written.  With `--config-file` it is implied by `MODEL.RPN_ONLY True` among the
 overrides (the evaluation pass itself then already logs the recalls: engine/inference.py sends proposals there).
-`--expected TASK METRIC MEAN STD` (repeatable) is the reference's TEST.EXPECTED_RESULTS sanity band."""
+`--expected TASK METRIC MEAN STD` (repeatable) is the reference's TEST.EXPECTED_RESULTS sanity band.
+
+`--metric voc07` / `voc12` scores the same predictions PASCAL-VOC-style instead (AP per class and mAP at
+`--voc-iou`, default 0.5; 11-point or area metric; a crowd annotation counts as `difficult`), which is the number the
+domain-adaptation papers report, and writes `result.txt`.  `--dataset voc:DIR,SPLIT` names a set in PASCAL VOC layout; it has
+no COCO form, so it is always scored VOC-style (`--metric coco` is then read as voc07, the reference's default), and with
+`--config-file` its evaluation pass runs in this process (one GPU) and leaves `predictions.pth` in
+`<output-dir>/inference/<DIR's name>_<SPLIT>/`: tools/test_net_da.py takes COCO-format sets only."""
 import argparse
 import logging
 import os
@@ -28,13 +35,40 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from da_detect_amd.data.datasets import COCODataset  # noqa: E402
+from da_detect_amd.data.build import dataset_from_spec  # noqa: E402
 from da_detect_amd.data.evaluation import evaluate  # noqa: E402
+from da_detect_amd.data.evaluation.voc import do_voc_evaluation  # noqa: E402
 
 
 def _pair(text):
     ann, root = text.split(",")
     return ann, root
+
+
+def _voc_evaluation_pass(args, folder):
+    """the evaluation pass over a VOC-layout set, in this process (tools/test_net_da.py builds COCO records, which such a set
+    has no ids for): detector, weights, test loader, engine.inference — it leaves predictions.pth in `folder`"""
+    from da_detect_amd.config import cfg
+    from da_detect_amd.data.build import make_test_data_loader
+    from da_detect_amd.data.transforms import build_transforms
+    from da_detect_amd.engine.inference import inference
+    from da_detect_amd.modeling.detector import build_detection_model
+    from da_detect_amd.utils.checkpoint import DetectronCheckpointer
+
+    if not torch.cuda.is_available():
+        raise SystemExit("score_net_da.py needs a HIP device: the product path has no CPU fallback")
+    c = cfg.clone()
+    c.merge_from_file(args.config_file)
+    c.merge_from_list(args.opts)
+    c.freeze()
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = build_detection_model(c).to(device)
+    DetectronCheckpointer(c, model, save_dir=args.output_dir).load(args.ckpt if args.ckpt else c.MODEL.WEIGHT)
+    model.eval()
+    dataset = dataset_from_spec(args.dataset, build_transforms(c, is_train=False), is_train=False)
+    os.makedirs(folder, exist_ok=True)
+    inference(model, make_test_data_loader(c, dataset), dataset_name=",".join(args.dataset), box_only=c.MODEL.RPN_ONLY,
+              device=device, output_folder=folder, evaluate=lambda **_: None)      # scored below, from the saved file
 
 
 def main():
@@ -47,6 +81,9 @@ def main():
     ap.add_argument("--proposals", action="store_true", help="score proposal recall instead of box AP")
     ap.add_argument("--expected", nargs=4, action="append", default=[], metavar=("TASK", "METRIC", "MEAN", "STD"))
     ap.add_argument("--sigma-tol", type=float, default=4)
+    ap.add_argument("--metric", choices=("coco", "voc07", "voc12"), default="coco",
+                    help="coco: COCO box AP (default); voc07 / voc12: PASCAL VOC AP, 11-point / area metric")
+    ap.add_argument("--voc-iou", type=float, nargs="+", default=[0.5], help="IoU threshold(s) of the VOC metrics")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE overrides of the yaml (with --config-file)")
     args = ap.parse_args()
     if (args.predictions is None) == (args.config_file is None):
@@ -54,11 +91,18 @@ def main():
     if args.config_file is not None:
         if not args.output_dir:
             raise SystemExit("--config-file needs --output-dir: the evaluation pass leaves predictions.pth there")
-        run = [sys.executable, os.path.join(ROOT, "tools", "test_net_da.py"), "--config-file", args.config_file, "--dataset",
-               ",".join(args.dataset), "--output-dir", args.output_dir] + (["--ckpt", args.ckpt] if args.ckpt else []) + args.opts
-        subprocess.check_call(run)
-        name = os.path.splitext(os.path.basename(args.dataset[0]))[0]
-        args.predictions = os.path.join(args.output_dir, "inference", name, "predictions.pth")
+        logging.basicConfig(level=logging.INFO)
+        voc = args.dataset[0].startswith("voc:")
+        name = os.path.basename(args.dataset[0][len("voc:"):].rstrip("/")) + "_" + args.dataset[1] if voc else \
+            os.path.splitext(os.path.basename(args.dataset[0]))[0]
+        folder = os.path.join(args.output_dir, "inference", name)
+        if voc:
+            _voc_evaluation_pass(args, folder)
+        else:
+            run = [sys.executable, os.path.join(ROOT, "tools", "test_net_da.py"), "--config-file", args.config_file, "--dataset",
+                   ",".join(args.dataset), "--output-dir", args.output_dir] + (["--ckpt", args.ckpt] if args.ckpt else []) + args.opts
+            subprocess.check_call(run)
+        args.predictions = os.path.join(folder, "predictions.pth")
         rpn_only = [v for k, v in zip(args.opts[::2], args.opts[1::2]) if k == "MODEL.RPN_ONLY"]
         args.proposals = args.proposals or (bool(rpn_only) and rpn_only[-1].lower() in ("true", "1"))
     if not args.proposals and not torch.cuda.is_available():
@@ -67,12 +111,19 @@ def main():
     logging.basicConfig(level=logging.INFO)
     log = logging.getLogger("maskrcnn_benchmark.score_net")
     ann, root = args.dataset
-    dataset = COCODataset(ann, root, remove_images_without_annotations=False)
+    dataset = dataset_from_spec(args.dataset, None, is_train=False)
     predictions = torch.load(args.predictions, weights_only=False)
     if len(predictions) != len(dataset):
         raise SystemExit("%d predictions for %d images: not this dataset's predictions.pth" % (len(predictions), len(dataset)))
+    folder = os.path.dirname(os.path.abspath(args.predictions))
+    if not args.proposals and (args.metric != "coco" or ann.startswith("voc:")):
+        result = do_voc_evaluation(dataset, predictions, folder, log, iou_thresh=args.voc_iou[0] if len(args.voc_iou) == 1
+                                   else args.voc_iou, use_07_metric=args.metric != "voc12")
+        for iou, row in zip(args.voc_iou, result.get("ap_by_iou", ())):
+            log.info("IoU %.2f: mAP %.4f", iou, float(row[row == row].mean()) if (row == row).any() else float("nan"))
+        return
     expected = [(task, metric, (float(mean), float(std))) for task, metric, mean, std in args.expected]
-    out = evaluate(dataset, predictions, os.path.dirname(os.path.abspath(args.predictions)), box_only=args.proposals,
+    out = evaluate(dataset, predictions, folder, box_only=args.proposals,
                    iou_types=("bbox",), expected_results=expected, expected_results_sigma_tol=args.sigma_tol)
     if out is not None:
         results, records = out

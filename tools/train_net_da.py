@@ -9,8 +9,8 @@ then engine.trainer.do_da_train.  One process per GPU:
     python tools/train_net_da.py --config-file <yaml> --synthetic 20        # no dataset: 20 seeded synthetic steps
 
 Differences to the reference script, on purpose: DistributedDataParallel is replaced by the bucketed gradient reducer
-attached to the fused optimizer (parallel/reducer.py); datasets are named by (annotation file, image root) pairs instead
-of the path catalog; there is no periodic evaluation (engine.inference.inference produces the bbox.json records)."""
+attached to the fused optimizer (parallel/reducer.py); datasets are named by (annotation file, image root) pairs — or
+`voc:DIR,SPLIT` for PASCAL VOC layout — instead of the path catalog; there is no periodic evaluation (engine.inference.inference produces the bbox.json records)."""
 import argparse
 import logging
 import os
@@ -52,7 +52,8 @@ def _pair(text):
 def main():
     ap = argparse.ArgumentParser(description="DA Faster R-CNN training on MI355X")
     ap.add_argument("--config-file", required=True)
-    ap.add_argument("--source", type=_pair)
+    ap.add_argument("--source", type=_pair, help="ann.json,imgdir — or voc:DIR,SPLIT for a dataset in PASCAL VOC layout "
+                                                 "(likewise --target and --auxiliary)")
     ap.add_argument("--target", type=_pair)
     ap.add_argument("--auxiliary", type=_pair)
     ap.add_argument("--synthetic", type=int, default=0, help="run N steps on seeded synthetic batches instead of datasets")

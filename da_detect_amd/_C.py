@@ -122,12 +122,12 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _dev(t, name):
+def _dev(t, name, dtype=torch.float32):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise _lib.DadetError(
             "%s must be a tensor on the HIP device: the da_detect_amd operators have no CPU path" % name)
-    if t.dtype != torch.float32:
-        raise _lib.DadetError("%s must be float32, got %s" % (name, t.dtype))
+    if t.dtype != dtype:
+        raise _lib.DadetError("%s must be %s, got %s" % (name, dtype, t.dtype))
     return t
 
 
@@ -262,16 +262,26 @@ def _f64_table(values):
     return (ctypes.c_double * max(len(values), 1))(*values), len(values)
 
 
-def coco_match_workspace_bytes(det_off, gt_off, n_det, n_gt, n_thr, n_area):
-    """scratch of coco_match for these offset tables; validates them on the host exactly as the launch does (no device)"""
+def _pair_tables(who, det_off, gt_off):
+    """host copies of the two offset tables of a pair matcher and the number of pairs"""
     d_host, nd = _int_table(det_off)
     g_host, ng = _int_table(gt_off)
     if nd != ng or nd < 1:
-        raise _lib.DadetError("coco_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
+        raise _lib.DadetError("%s: the offset tables need pairs + 1 entries each, got %d and %d" % (who, nd, ng))
+    return d_host, g_host, nd - 1
+
+
+def _query_bytes(symbol, *args):
+    """the byte count a `*_workspace_bytes` entry of the library answers for these arguments"""
     nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_coco_match_workspace_bytes", d_host, g_host, nd - 1, int(n_det), int(n_gt), int(n_thr), int(n_area),
-              ctypes.byref(nbytes))
+    _lib.call(symbol, *args, ctypes.byref(nbytes))
     return nbytes.value
+
+
+def coco_match_workspace_bytes(det_off, gt_off, n_det, n_gt, n_thr, n_area):
+    """scratch of coco_match for these offset tables; validates them on the host exactly as the launch does (no device)"""
+    d_host, g_host, pairs = _pair_tables("coco_match", det_off, gt_off)
+    return _query_bytes("dadet_coco_match_workspace_bytes", d_host, g_host, pairs, int(n_det), int(n_gt), int(n_thr), int(n_area))
 
 
 def coco_match(det_box, gt_box, gt_area, gt_crowd, det_off, gt_off, iou_thr, area_rng):
@@ -279,29 +289,19 @@ def coco_match(det_box, gt_box, gt_area, gt_crowd, det_off, gt_off, iou_thr, are
     xywh float64, gt_area [Ng] float64, gt_crowd [Ng] int32 on the device; det_off / gt_off host ints [P + 1] (pair p's slices;
     detections best first, at most COCO_MATCH_MAX_DETS); iou_thr [T] and area_rng [A][2] host floats ->
     (matched uint8 [T, A, Nd], ignored uint8 [T, A, Nd], npig int32 [P, A]) on the device."""
-    for t, name, dtype in ((det_box, "det_box", torch.float64), (gt_box, "gt_box", torch.float64),
-                           (gt_area, "gt_area", torch.float64), (gt_crowd, "gt_crowd", torch.int32)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.DadetError(
-                "%s must be a tensor on the HIP device: the da_detect_amd operators have no CPU path" % name)
-        if t.dtype != dtype:
-            raise _lib.DadetError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    det_box, gt_box, gt_area, gt_crowd = det_box.contiguous(), gt_box.contiguous(), gt_area.contiguous(), gt_crowd.contiguous()
+    det_box = _dev(det_box, "det_box", torch.float64).contiguous()
+    gt_box = _dev(gt_box, "gt_box", torch.float64).contiguous()
+    gt_area = _dev(gt_area, "gt_area", torch.float64).contiguous()
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.int32).contiguous()
     n_det, n_gt = int(det_box.shape[0]), int(gt_box.shape[0])
     if det_box.numel() != 4 * n_det or gt_box.numel() != 4 * n_gt or gt_area.numel() != n_gt or gt_crowd.numel() != n_gt:
         raise _lib.DadetError("coco_match: boxes must be [n, 4], gt_area and gt_crowd [n_gt]")
-    d_host, nd = _int_table(det_off)
-    g_host, ng = _int_table(gt_off)
-    if nd != ng or nd < 1:
-        raise _lib.DadetError("coco_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
-    pairs = nd - 1
+    d_host, g_host, pairs = _pair_tables("coco_match", det_off, gt_off)
     thr_host, T = _f64_table(iou_thr)
     rng_host, A2 = _f64_table([v for lo_hi in area_rng for v in lo_hi])
     A = A2 // 2
     dev = det_box.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_coco_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T, A, ctypes.byref(nbytes))
-    ws = _workspace(nbytes.value, dev)
+    ws = _workspace(_query_bytes("dadet_coco_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T, A), dev)
     matched = torch.empty((T, A, n_det), dtype=torch.uint8, device=dev)
     ignored = torch.empty((T, A, n_det), dtype=torch.uint8, device=dev)
     npig = torch.empty((pairs, A), dtype=torch.int32, device=dev)
@@ -315,13 +315,8 @@ VOC_MATCH_MAX_THRESHOLDS = 16    # IoU thresholds per launch (csrc/voc_match.hip
 
 def voc_match_workspace_bytes(det_off, gt_off, n_det, n_gt, n_thr):
     """scratch of voc_match for these offset tables; validates them on the host exactly as the launch does (no device)"""
-    d_host, nd = _int_table(det_off)
-    g_host, ng = _int_table(gt_off)
-    if nd != ng or nd < 1:
-        raise _lib.DadetError("voc_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
-    nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_voc_match_workspace_bytes", d_host, g_host, nd - 1, int(n_det), int(n_gt), int(n_thr), ctypes.byref(nbytes))
-    return nbytes.value
+    d_host, g_host, pairs = _pair_tables("voc_match", det_off, gt_off)
+    return _query_bytes("dadet_voc_match_workspace_bytes", d_host, g_host, pairs, int(n_det), int(n_gt), int(n_thr))
 
 
 def voc_match(det_box, gt_box, gt_difficult, det_off, gt_off, iou_thr):
@@ -329,27 +324,16 @@ def voc_match(det_box, gt_box, gt_difficult, det_off, gt_off, iou_thr):
     xyxy float32, gt_difficult [Ng] uint8 on the device; det_off / gt_off host ints [P + 1] (pair p's slices; detections best
     first, any number); iou_thr [T <= VOC_MATCH_MAX_THRESHOLDS] host floats ->
     (match int8 [T, Nd] in {-1, 0, 1}, n_pos int32 [P], gt_index int32 [Nd], iou_max float32 [Nd]) on the device."""
-    for t, name, dtype in ((det_box, "det_box", torch.float32), (gt_box, "gt_box", torch.float32),
-                           (gt_difficult, "gt_difficult", torch.uint8)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.DadetError(
-                "%s must be a tensor on the HIP device: the da_detect_amd operators have no CPU path" % name)
-        if t.dtype != dtype:
-            raise _lib.DadetError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    det_box, gt_box, gt_difficult = det_box.contiguous(), gt_box.contiguous(), gt_difficult.contiguous()
+    det_box = _dev(det_box, "det_box").contiguous()
+    gt_box = _dev(gt_box, "gt_box").contiguous()
+    gt_difficult = _dev(gt_difficult, "gt_difficult", torch.uint8).contiguous()
     n_det, n_gt = int(det_box.shape[0]), int(gt_box.shape[0])
     if det_box.numel() != 4 * n_det or gt_box.numel() != 4 * n_gt or gt_difficult.numel() != n_gt:
         raise _lib.DadetError("voc_match: boxes must be [n, 4], gt_difficult [n_gt]")
-    d_host, nd = _int_table(det_off)
-    g_host, ng = _int_table(gt_off)
-    if nd != ng or nd < 1:
-        raise _lib.DadetError("voc_match: the offset tables need pairs + 1 entries each, got %d and %d" % (nd, ng))
-    pairs = nd - 1
+    d_host, g_host, pairs = _pair_tables("voc_match", det_off, gt_off)
     thr_host, T = _f64_table(iou_thr)
     dev = det_box.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_voc_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T, ctypes.byref(nbytes))
-    ws = _workspace(nbytes.value, dev)
+    ws = _workspace(_query_bytes("dadet_voc_match_workspace_bytes", d_host, g_host, pairs, n_det, n_gt, T), dev)
     match = torch.empty((T, n_det), dtype=torch.int8, device=dev)
     n_pos = torch.empty(pairs, dtype=torch.int32, device=dev)
     gt_index = torch.empty(n_det, dtype=torch.int32, device=dev)

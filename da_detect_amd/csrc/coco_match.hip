@@ -10,10 +10,7 @@
 // The pair's scratch (matrix, one flag byte per ground truth, one "taken" byte per ground truth and variant) lives in LDS when
 // it fits the 160 KiB of a CU and in the caller's workspace otherwise; the launch asks for the LDS of the largest pair
 // that fits.  No atomics, nothing depends on timing: every byte of the output has exactly one writer.
-#include <algorithm>
-#include <vector>
-
-#include "common.h"
+#include "pair_tables.h"
 
 namespace dadet {
 namespace {
@@ -132,51 +129,22 @@ __global__ __launch_bounds__(kCocoThreads) void coco_match_kernel(
   }
 }
 
-// Host-side checks shared by the query and the launch: both tables start at 0, never decrease, end at the array sizes, and
-// no pair holds more than kCocoMaxDet detections.  Fills the workspace layout.
-struct CocoLayout {
-  size_t tables;          // det_off | gt_off | ws_off
-  size_t total;
-  size_t lds;             // dynamic LDS of the launch
-  std::vector<long long> ws_off;
-};
-
+// The checks shared by the query and the launch: the threshold and area counts, then the offset tables (pair_tables.h), where
+// no pair may hold more than kCocoMaxDet detections.
 int coco_layout(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt, int n_thr, int n_area,
-                CocoLayout* out) {
-  DADET_REQUIRE(pairs >= 0 && n_det >= 0 && n_gt >= 0, "coco_match: negative size (pairs %d, n_det %d, n_gt %d)", pairs, n_det,
-                n_gt);
+                PairLayout* out) {
   DADET_REQUIRE(n_thr >= 1 && n_thr <= kCocoMaxThr && n_area >= 1 && n_area <= kCocoMaxArea && n_thr * n_area <= kCocoMaxLanes,
                 "coco_match: %d thresholds x %d area ranges; at most %d x %d and %d variants", n_thr, n_area, kCocoMaxThr,
                 kCocoMaxArea, kCocoMaxLanes);
-  DADET_REQUIRE(det_off_host && gt_off_host, "coco_match: null offset table");
-  DADET_REQUIRE(det_off_host[0] == 0 && gt_off_host[0] == 0, "coco_match: offset tables must start at 0 (%d, %d)", det_off_host[0],
-                gt_off_host[0]);
   const int lanes = n_thr * n_area;
-  const size_t tables = ((sizeof(int) * 2 * (size_t)(pairs + 1) + 7) & ~(size_t)7) + sizeof(long long) * (size_t)std::max(pairs, 1);
-  size_t at = (tables + 255) & ~(size_t)255, lds = 0;
-  out->ws_off.assign((size_t)std::max(pairs, 1), -1);
-  for (int p = 0; p < pairs; ++p) {
-    const int D = det_off_host[p + 1] - det_off_host[p], G = gt_off_host[p + 1] - gt_off_host[p];
-    DADET_REQUIRE(D >= 0 && G >= 0, "coco_match: offsets decrease at pair %d", p);
-    DADET_REQUIRE(det_off_host[p + 1] <= n_det && gt_off_host[p + 1] <= n_gt,
-                  "coco_match: offsets of pair %d (%d, %d) run past the arrays (%d, %d)", p, det_off_host[p + 1], gt_off_host[p + 1],
-                  n_det, n_gt);
-    DADET_REQUIRE(D <= kCocoMaxDet, "coco_match: pair %d has %d detections; at most %d after the cut", p, D, kCocoMaxDet);
-    const size_t need = coco_scratch_bytes(D, G, lanes);
-    if (need <= kCocoLdsLimit) {
-      lds = std::max(lds, need);
-    } else {
-      out->ws_off[p] = (long long)at;
-      at += need;
-    }
-  }
-  DADET_REQUIRE(det_off_host[pairs] == n_det && gt_off_host[pairs] == n_gt,
-                "coco_match: offset tables end at (%d, %d), the arrays hold (%d, %d)", det_off_host[pairs], gt_off_host[pairs], n_det,
-                n_gt);
-  out->tables = tables;
-  out->total = at;
-  out->lds = lds;
-  return DADET_OK;
+  return pair_layout("coco_match", kCocoLdsLimit, det_off_host, gt_off_host, pairs, n_det, n_gt,
+                     [lanes](int p, int D, int G, size_t* need) {
+                       DADET_REQUIRE(D <= kCocoMaxDet, "coco_match: pair %d has %d detections; at most %d after the cut", p, D,
+                                     kCocoMaxDet);
+                       *need = coco_scratch_bytes(D, G, lanes);
+                       return DADET_OK;
+                     },
+                     out);
 }
 
 }  // namespace
@@ -187,7 +155,7 @@ using namespace dadet;
 extern "C" int dadet_coco_match_workspace_bytes(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt,
                                                 int n_thr, int n_area, size_t* bytes_out) {
   DADET_REQUIRE(bytes_out, "coco_match_workspace_bytes: null output");
-  CocoLayout lay;
+  PairLayout lay;
   const int rc = coco_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, n_area, &lay);
   if (rc != DADET_OK) return rc;
   *bytes_out = lay.total;
@@ -199,8 +167,8 @@ extern "C" int dadet_coco_match(const double* det_box, const double* gt_box, con
                                 const double* iou_thr_host, int n_thr, const double* area_rng_host, int n_area, void* workspace,
                                 size_t workspace_bytes, unsigned char* matched_out, unsigned char* ignored_out, int* npig_out,
                                 void* stream) {
-  CocoLayout lay;
-  const int rc = coco_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, n_area, &lay);
+  PairLayout lay;
+  int rc = coco_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, n_area, &lay);
   if (rc != DADET_OK) return rc;
   DADET_REQUIRE(iou_thr_host && area_rng_host, "coco_match: null threshold / area table");
   if (pairs == 0) return DADET_OK;
@@ -223,26 +191,13 @@ extern "C" int dadet_coco_match(const double* det_box, const double* gt_box, con
 
   hipStream_t st = as_stream(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  int* d_det_off = reinterpret_cast<int*>(ws);
-  int* d_gt_off = d_det_off + (pairs + 1);
-  long long* d_ws_off = reinterpret_cast<long long*>(ws + ((sizeof(int) * 2 * (size_t)(pairs + 1) + 7) & ~(size_t)7));
-  // the validated tables themselves go to the device: what the kernel indexes with is what was checked above.  ws_off dies
-  // with this call, so the upload is waited for (the tables are a few KB; the one host wait of this entry point).
-  if (hipMemcpyAsync(d_det_off, det_off_host, sizeof(int) * (size_t)(pairs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_gt_off, gt_off_host, sizeof(int) * (size_t)(pairs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_ws_off, lay.ws_off.data(), sizeof(long long) * (size_t)pairs, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("coco_match: upload of the offset tables failed");
-    return DADET_ELAUNCH;
-  }
+  const int *d_det_off, *d_gt_off;
+  const long long* d_ws_off;
+  rc = pair_tables_upload("coco_match", lay, det_off_host, gt_off_host, pairs, ws, st, &d_det_off, &d_gt_off, &d_ws_off);
+  if (rc != DADET_OK) return rc;
   if (lay.lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(coco_match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lay.lds);
-    if (e != hipSuccess) {
-      set_error("coco_match: hipFuncSetAttribute(%zu B LDS): %s", lay.lds, hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
+    rc = raise_lds("coco_match", coco_match_kernel, lay.lds);
+    if (rc != DADET_OK) return rc;
   }
   hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)pairs), dim3(kCocoThreads), lay.lds, st, det_box, gt_box, gt_area, gt_crowd,
                      d_det_off, d_gt_off, d_ws_off, ws, prm, n_det, matched_out, ignored_out, npig_out);

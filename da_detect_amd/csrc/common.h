@@ -27,6 +27,26 @@ inline int check_launch(const char* what) {
     }                                       \
   } while (0)
 
+// Lets `kernel` be launched with up to `bytes` of dynamic LDS (launches above 48 KiB need it).
+template <typename K>
+inline int raise_lds(const char* who, K* kernel, size_t bytes) {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) {
+    set_error("%s: hipFuncSetAttribute(%zu B LDS): %s", who, bytes, hipGetErrorString(e));
+    return DADET_ELAUNCH;
+  }
+  return DADET_OK;
+}
+
+// The same, once: `done` is the caller's own static flag for this kernel (per process, not per device: one process drives one GPU).
+template <typename K>
+inline int raise_lds_once(bool* done, const char* who, K* kernel, size_t bytes) {
+  if (*done) return DADET_OK;
+  const int rc = raise_lds(who, kernel, bytes);
+  *done = rc == DADET_OK;
+  return rc;
+}
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -1176,16 +1176,9 @@ int launch_fwd_big(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st) {
   const size_t lds = 16 + (variant == 2 ? 2 * (2 * 256 * 64 + 2 * 128 * 64) + 12 * 512 * sizeof(int)
                                         : 2 * 4 * 256 * 64 + 16 * 256 * sizeof(int));
   static bool attr_set[3] = {false, false, false};
-  if (!attr_set[variant]) {
-    const void* fn = variant == 2 ? reinterpret_cast<const void*>(conv_big128_kernel)
-                                  : reinterpret_cast<const void*>(conv_big_kernel<256>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_forward(big): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set[variant] = true;
-  }
+  const void* fn = variant == 2 ? reinterpret_cast<const void*>(conv_big128_kernel)
+                                : reinterpret_cast<const void*>(conv_big_kernel<256>);
+  if (const int rc = raise_lds_once(&attr_set[variant], "conv_forward(big)", fn, lds); rc != DADET_OK) return rc;
   if (variant == 2) hipLaunchKernelGGL(conv_big128_kernel, dim3(p.grid), dim3(512), lds, st, a);
   else hipLaunchKernelGGL((conv_big_kernel<256>), dim3(p.grid), dim3(512), lds, st, a);
   return check_launch("conv_forward(big)");
@@ -1196,30 +1189,15 @@ constexpr size_t kWgradBigLds = 2 * 4 * 256 * 64 + 2 * 256 * sizeof(int4);      
 
 int launch_wgrad_big(WgradArgs& a, hipStream_t st) {
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_big_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradBigLds);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad(big): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "conv_wgrad(big)", conv_wgrad_big_kernel, kWgradBigLds); rc != DADET_OK) return rc;
   hipLaunchKernelGGL(conv_wgrad_big_kernel, dim3(a.tiles_co * a.tiles_kc * a.splits), dim3(512), kWgradBigLds, st, a);
   return check_launch("conv_wgrad(big)");
 }
 
 int launch_wgrad_big_group(const WgradArgs* a, const int n, hipStream_t st) {
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_big_group_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradBigLds);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_group: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "conv_wgrad_group", conv_wgrad_big_group_kernel, kWgradBigLds); rc != DADET_OK)
+    return rc;
   WgradGroup g;
   g.n = n;
   int at = 0;

@@ -376,15 +376,8 @@ static int launch_fwd(ConvArgs& a, hipStream_t st) {
   constexpr int BM = 2 * TM * 32, BN = 2 * TN * 32;
   const size_t lds = sizeof(float) * (BM + BN) * LDS_STRIDE;
   static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_kernel<TM, TN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_forward: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = raise_lds_once(&attr_set, "conv_forward", conv_fwd_kernel<TM, TN>, lds); rc != DADET_OK) return rc;
   hipLaunchKernelGGL((conv_fwd_kernel<TM, TN>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, st, a);
   return check_launch("conv_forward");
 }
@@ -397,15 +390,7 @@ int launch_fwd_exact(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st) {
 int launch_wgrad_exact(WgradArgs& a, hipStream_t st) {
   const size_t lds = sizeof(float) * 2 * 32 * 128;  // 32 KB: three workgroups per CU
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "conv_wgrad", conv_wgrad_kernel, lds); rc != DADET_OK) return rc;
   hipLaunchKernelGGL(conv_wgrad_kernel, dim3(a.tiles_co * a.tiles_kc, a.splits), dim3(256), lds, st, a);
   return check_launch("conv_wgrad");
 }

@@ -569,15 +569,9 @@ static int launch_split(ConvArgs& a, const int ksplits, hipStream_t st) {
   constexpr int BM = 2 * TM * 32, BN = 2 * TN * 32;
   const size_t lds = sizeof(__bf16) * TERMS * (BM + BN) * PLANE_STRIDE;
   static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_split_kernel<TM, TN, FMT, AB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_forward(split): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = raise_lds_once(&attr_set, "conv_forward(split)", conv_fwd_split_kernel<TM, TN, FMT, AB>, lds); rc != DADET_OK)
+      return rc;
   hipLaunchKernelGGL((conv_fwd_split_kernel<TM, TN, FMT, AB>), dim3(a.tiles_m * a.tiles_n, ksplits), dim3(256), lds,
                      st, a);
   return check_launch("conv_forward(split)");
@@ -588,15 +582,8 @@ static int launch_split_sk(ConvArgs& a, hipStream_t st) {
   constexpr int TERMS = Fmt<FMT>::terms;
   const size_t lds = sizeof(__bf16) * TERMS * 256 * PLANE_STRIDE;
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_split_sk_kernel<FMT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_forward(split, stream-K): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "conv_forward(split, stream-K)", conv_fwd_split_sk_kernel<FMT>, lds); rc != DADET_OK)
+    return rc;
   hipLaunchKernelGGL((conv_fwd_split_sk_kernel<FMT>), dim3(a.sk_dp_tiles + a.sk_units), dim3(256), lds, st, a);
   return check_launch("conv_forward(split, stream-K)");
 }
@@ -918,15 +905,10 @@ static int launch_wgrad_group_terms(const WgradGroup& g, hipStream_t st) {
   constexpr int TERMS = Fmt<FMT>::terms;
   const size_t lds = sizeof(__bf16) * TERMS * 2 * 128 * PLANE_STRIDE;
   static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_split_group_kernel<FMT, SMALL_MAP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_group(split): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = raise_lds_once(&attr_set, "conv_wgrad_group(split)", conv_wgrad_split_group_kernel<FMT, SMALL_MAP>, lds);
+        rc != DADET_OK)
+      return rc;
   hipLaunchKernelGGL((conv_wgrad_split_group_kernel<FMT, SMALL_MAP>), dim3(g.first[kWgradGroupMax]), dim3(256), lds, st, g);
   return check_launch("conv_wgrad_group(split)");
 }
@@ -950,15 +932,9 @@ static int launch_wgrad_terms(WgradArgs& a, hipStream_t st) {
   constexpr int TERMS = Fmt<FMT>::terms;
   const size_t lds = sizeof(__bf16) * TERMS * 2 * 128 * PLANE_STRIDE;
   static bool attr_set = false;
-  if (!attr_set && lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_split_kernel<FMT, SMALL_MAP>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad(split): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = raise_lds_once(&attr_set, "conv_wgrad(split)", conv_wgrad_split_kernel<FMT, SMALL_MAP>, lds); rc != DADET_OK)
+      return rc;
   hipLaunchKernelGGL((conv_wgrad_split_kernel<FMT, SMALL_MAP>), dim3(a.tiles_co * a.tiles_kc, a.splits), dim3(256),
                      lds, st, a);
   return check_launch("conv_wgrad(split)");

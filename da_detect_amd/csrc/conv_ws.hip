@@ -354,15 +354,9 @@ template <int K, int BN, int FMT, int EROWS = 32>
 static int launch_ws(ConvArgs& a, const plan::FwdPlan& p, hipStream_t st) {
   const size_t lds = (size_t)Fmt<FMT>::terms * BN * (K + 8) * 2 + 8 * EROWS * EPI_STRIDE * 4 + 2 * BN * 4;
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_ws_kernel<K, BN, FMT, EROWS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv_forward(weight-stationary 1x1): hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "conv_forward(weight-stationary 1x1)", conv1x1_ws_kernel<K, BN, FMT, EROWS>, lds);
+      rc != DADET_OK)
+    return rc;
   // 1 - 3 launches over ranges of column panels (conv_plan.h: ws_plan)
   a.ws_panel0 = 0;
   for (int i = 0; i < p.ws_parts; ++i) {

@@ -636,15 +636,8 @@ static int deform_sample_backward_impl(const float* x, const float* offset, cons
     const int tiles_x = ceil_div(g.Wo, kDTile), tiles_y = ceil_div(g.Ho, kDTile);
     const size_t lds = sizeof(float) * kDWin * kDWin * kDChunk;
     static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(deform_sample_bwd_lds_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        set_error("deform_sample_backward: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return DADET_ELAUNCH;
-      }
-      attr_set = true;
-    }
+    if (const int rc = raise_lds_once(&attr_set, "deform_sample_backward", deform_sample_bwd_lds_kernel, lds); rc != DADET_OK)
+      return rc;
     static const bool window = getenv("DADET_DEFORM_BWD_LDS") && getenv("DADET_DEFORM_BWD_LDS")[0] == '1';
     const size_t lists = (size_t)g.N * (g.H + 1) * (g.W + 1) * g.dg;
     const size_t need = lists * sizeof(int) + 256 + lists * kListCap * sizeof(ListEntry);

@@ -418,14 +418,8 @@ extern "C" int dadet_detect_post(const float* boxes, const float* scores, const 
   while (p2 < n_max) p2 <<= 1;
   const int threads = p2 / 2 >= 1024 ? 1024 : (p2 / 2 < 64 ? 64 : p2 / 2);
   const size_t lds = sizeof(unsigned long long) * (size_t)p2;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(post_rank_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("detect_post: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-  }
+  if (lds > 48 * 1024)
+    if (const int rc = raise_lds("detect_post", post_rank_kernel, lds); rc != DADET_OK) return rc;
   hipLaunchKernelGGL(post_rank_kernel, dim3(S), dim3(threads), lds, st, boxes4, scores, imgs, num_classes, n_max,
                      score_thresh, ranked, rowmap, cand);
 

@@ -821,14 +821,8 @@ extern "C" int dadet_nms(const float* boxes_xyxy, const float* scores, int n, fl
   } else if (p2 <= kSortLdsMax) {
     const int threads = p2 / 2 >= 1024 ? 1024 : (p2 / 2 < 64 ? 64 : p2 / 2);
     const size_t lds = sizeof(Key) * (size_t)p2;
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nms_sort_lds_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        set_error("nms: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-        return DADET_ELAUNCH;
-      }
-    }
+    if (lds > 48 * 1024)
+      if (const int rc = raise_lds("nms", nms_sort_lds_kernel, lds); rc != DADET_OK) return rc;
     hipLaunchKernelGGL(nms_sort_lds_kernel, dim3(1), dim3(threads), lds, st, scores, n, p2, order);
   } else {
     Key* keys = reinterpret_cast<Key*>(base + ws.keys_off);

@@ -365,16 +365,10 @@ extern "C" int dadet_proposals_sample(const float* sorted_boxes, const float* so
   while (N < post_n + num_appended) N <<= 1;
   const size_t lds = (sizeof(uint64_t) + sizeof(int)) * (size_t)N + (size_t)G * 20;
   static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(proposals_sample_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)((sizeof(uint64_t) + sizeof(int)) * kSampleMaxN + 1024 * 20));
-    if (e != hipSuccess) {
-      set_error("proposals_sample: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "proposals_sample", proposals_sample_kernel,
+                                    (sizeof(uint64_t) + sizeof(int)) * kSampleMaxN + 1024 * 20);
+      rc != DADET_OK)
+    return rc;
   hipLaunchKernelGGL(proposals_sample_kernel, dim3(1), dim3(kSampleThreads), lds, as_stream(stream),
                      reinterpret_cast<const float4*>(sorted_boxes), sorted_scores, keep, count_dev, post_n,
                      reinterpret_cast<const float4*>(appended_boxes), num_appended,

@@ -476,16 +476,10 @@ extern "C" int dadet_topk_sorted_rows(const dadet_topk_row* rows_in, int rows, v
   while (sort_n < k_max) sort_n <<= 1;
   const size_t lds = sizeof(unsigned long long) * (size_t)sort_n + sizeof(int) * (2048 + kTopkTieCap);
   static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_rows_finish_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(sizeof(unsigned long long) * kTopkCap + sizeof(int) * (2048 + kTopkTieCap)));
-    if (e != hipSuccess) {
-      set_error("topk_sorted_rows: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "topk_sorted_rows", topk_rows_finish_kernel,
+                                    sizeof(unsigned long long) * kTopkCap + sizeof(int) * (2048 + kTopkTieCap));
+      rc != DADET_OK)
+    return rc;
   hipLaunchKernelGGL(topk_rows_finish_kernel, dim3(rows), dim3(kTopkThreads), lds, st, tb, states, cand, k_max, ties, sort_n);
   return check_launch("topk_sorted_rows");
 }
@@ -502,16 +496,10 @@ extern "C" int dadet_topk_sorted(const float* scores, int rows, int n, int64_t r
   while (sort_n < k) sort_n <<= 1;
   const size_t lds = sizeof(unsigned long long) * (size_t)sort_n + sizeof(int) * (2048 + kTopkTieCap);
   static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(topk_sorted_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(sizeof(unsigned long long) * kTopkCap + sizeof(int) * (2048 + kTopkTieCap)));
-    if (e != hipSuccess) {
-      set_error("topk_sorted: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = raise_lds_once(&attr_set, "topk_sorted", topk_sorted_kernel,
+                                    sizeof(unsigned long long) * kTopkCap + sizeof(int) * (2048 + kTopkTieCap));
+      rc != DADET_OK)
+    return rc;
   hipLaunchKernelGGL(topk_sorted_kernel, dim3(rows), dim3(kTopkThreads), lds, as_stream(stream), scores, n, row_stride, k,
                      sort_n, out_scores, out_idx);
   return check_launch("topk_sorted");

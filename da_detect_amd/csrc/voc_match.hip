@@ -15,11 +15,9 @@
 // A minimum does not depend on the order of arrival, so the result is deterministic; every output byte has one writer.  No
 // D x G matrix exists and D is not capped.  A pair whose ground truths do not fit the 160 KiB of a CU keeps the same scratch
 // in the caller's workspace (the atomics then go to global memory, for that pair only).
-#include <algorithm>
 #include <climits>
-#include <vector>
 
-#include "common.h"
+#include "pair_tables.h"
 
 namespace dadet {
 namespace {
@@ -117,48 +115,15 @@ __global__ __launch_bounds__(kVocThreads) void voc_match_kernel(
   }
 }
 
-// Host-side checks shared by the query and the launch: both tables start at 0, never decrease and end at the array sizes.
-// Fills the workspace layout.
-struct VocLayout {
-  size_t tables;          // det_off | gt_off | ws_off
-  size_t total;
-  size_t lds;             // dynamic LDS of the launch
-  std::vector<long long> ws_off;
-};
-
-inline size_t voc_tables_head(int pairs) { return (sizeof(int) * 2 * (size_t)(pairs + 1) + 7) & ~(size_t)7; }
-
-int voc_layout(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt, int n_thr, VocLayout* out) {
-  DADET_REQUIRE(pairs >= 0 && n_det >= 0 && n_gt >= 0, "voc_match: negative size (pairs %d, n_det %d, n_gt %d)", pairs, n_det,
-                n_gt);
+// The checks shared by the query and the launch: the threshold count, then the offset tables (pair_tables.h).
+int voc_layout(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt, int n_thr, PairLayout* out) {
   DADET_REQUIRE(n_thr >= 1 && n_thr <= kVocMaxThr, "voc_match: %d thresholds; 1 to %d", n_thr, kVocMaxThr);
-  DADET_REQUIRE(det_off_host && gt_off_host, "voc_match: null offset table");
-  DADET_REQUIRE(det_off_host[0] == 0 && gt_off_host[0] == 0, "voc_match: offset tables must start at 0 (%d, %d)", det_off_host[0],
-                gt_off_host[0]);
-  const size_t tables = voc_tables_head(pairs) + sizeof(long long) * (size_t)std::max(pairs, 1);
-  size_t at = (tables + 255) & ~(size_t)255, lds = 0;
-  out->ws_off.assign((size_t)std::max(pairs, 1), -1);
-  for (int p = 0; p < pairs; ++p) {
-    const int D = det_off_host[p + 1] - det_off_host[p], G = gt_off_host[p + 1] - gt_off_host[p];
-    DADET_REQUIRE(D >= 0 && G >= 0, "voc_match: offsets decrease at pair %d", p);
-    DADET_REQUIRE(det_off_host[p + 1] <= n_det && gt_off_host[p + 1] <= n_gt,
-                  "voc_match: offsets of pair %d (%d, %d) run past the arrays (%d, %d)", p, det_off_host[p + 1], gt_off_host[p + 1],
-                  n_det, n_gt);
-    const size_t need = voc_scratch_bytes(G, n_thr);
-    if (need <= kVocLdsLimit) {
-      lds = std::max(lds, need);
-    } else {
-      out->ws_off[p] = (long long)at;
-      at += need;
-    }
-  }
-  DADET_REQUIRE(det_off_host[pairs] == n_det && gt_off_host[pairs] == n_gt,
-                "voc_match: offset tables end at (%d, %d), the arrays hold (%d, %d)", det_off_host[pairs], gt_off_host[pairs], n_det,
-                n_gt);
-  out->tables = tables;
-  out->total = at;
-  out->lds = lds;
-  return DADET_OK;
+  return pair_layout("voc_match", kVocLdsLimit, det_off_host, gt_off_host, pairs, n_det, n_gt,
+                     [n_thr](int, int, int G, size_t* need) {
+                       *need = voc_scratch_bytes(G, n_thr);
+                       return DADET_OK;
+                     },
+                     out);
 }
 
 }  // namespace
@@ -169,7 +134,7 @@ using namespace dadet;
 extern "C" int dadet_voc_match_workspace_bytes(const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt,
                                                int n_thr, size_t* bytes_out) {
   DADET_REQUIRE(bytes_out, "voc_match_workspace_bytes: null output");
-  VocLayout lay;
+  PairLayout lay;
   const int rc = voc_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, &lay);
   if (rc != DADET_OK) return rc;
   *bytes_out = lay.total;
@@ -180,8 +145,8 @@ extern "C" int dadet_voc_match(const float* det_box, const float* gt_box, const 
                                const int* det_off_host, const int* gt_off_host, int pairs, int n_det, int n_gt,
                                const double* iou_thr_host, int n_thr, void* workspace, size_t workspace_bytes,
                                signed char* match_out, int* n_pos_out, int* gt_index_out, float* iou_max_out, void* stream) {
-  VocLayout lay;
-  const int rc = voc_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, &lay);
+  PairLayout lay;
+  int rc = voc_layout(det_off_host, gt_off_host, pairs, n_det, n_gt, n_thr, &lay);
   if (rc != DADET_OK) return rc;
   DADET_REQUIRE(iou_thr_host, "voc_match: null threshold table");
   if (pairs == 0) return DADET_OK;
@@ -199,26 +164,13 @@ extern "C" int dadet_voc_match(const float* det_box, const float* gt_box, const 
 
   hipStream_t st = as_stream(stream);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  int* d_det_off = reinterpret_cast<int*>(ws);
-  int* d_gt_off = d_det_off + (pairs + 1);
-  long long* d_ws_off = reinterpret_cast<long long*>(ws + voc_tables_head(pairs));
-  // the validated tables themselves go to the device: what the kernel indexes with is what was checked above.  ws_off dies
-  // with this call, so the upload is waited for (the one host wait of this entry point).
-  if (hipMemcpyAsync(d_det_off, det_off_host, sizeof(int) * (size_t)(pairs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_gt_off, gt_off_host, sizeof(int) * (size_t)(pairs + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_ws_off, lay.ws_off.data(), sizeof(long long) * (size_t)pairs, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("voc_match: upload of the offset tables failed");
-    return DADET_ELAUNCH;
-  }
+  const int *d_det_off, *d_gt_off;
+  const long long* d_ws_off;
+  rc = pair_tables_upload("voc_match", lay, det_off_host, gt_off_host, pairs, ws, st, &d_det_off, &d_gt_off, &d_ws_off);
+  if (rc != DADET_OK) return rc;
   if (lay.lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(voc_match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lay.lds);
-    if (e != hipSuccess) {
-      set_error("voc_match: hipFuncSetAttribute(%zu B LDS): %s", lay.lds, hipGetErrorString(e));
-      return DADET_ELAUNCH;
-    }
+    rc = raise_lds("voc_match", voc_match_kernel, lay.lds);
+    if (rc != DADET_OK) return rc;
   }
   hipLaunchKernelGGL(voc_match_kernel, dim3((unsigned)pairs), dim3(kVocThreads), lay.lds, st, det_box, gt_box, gt_difficult,
                      d_det_off, d_gt_off, d_ws_off, ws, prm, n_det, match_out, n_pos_out, gt_index_out, iou_max_out);

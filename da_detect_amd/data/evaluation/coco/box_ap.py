@@ -11,7 +11,7 @@ import collections
 import numpy as np
 import torch
 
-from ...._lib import DadetError
+from .. import pairs
 
 IOU_THRESHOLDS = np.linspace(.5, .95, 10)
 RECALL_THRESHOLDS = np.linspace(0, 1, 101)
@@ -33,11 +33,6 @@ Packed = collections.namedtuple("Packed", [
 ])
 
 
-def _offsets(sorted_keys, pairs):
-    off = np.searchsorted(sorted_keys, pairs, side="left")
-    return np.append(off, len(sorted_keys)).astype(np.int32)
-
-
 def pack(records, dataset):
     """records: what engine.inference.prepare_for_coco_detection emits; dataset: `ids`, `anns_of`,
     `contiguous_category_id_to_json_id`"""
@@ -55,37 +50,25 @@ def pack(records, dataset):
         raise ValueError("a detection names image or category id %s, which the dataset does not have" % e)
     score = np.fromiter((r["score"] for r in records), dtype=np.float64, count=n)
     box = np.array([r["bbox"] for r in records], dtype=np.float64).reshape(-1, 4)
-    key = img * K + cat
-    order = np.lexsort((-score, key))          # stable: equal scores of a pair keep the record order
-    key_sorted = key[order]
-    first = np.searchsorted(key_sorted, key_sorted, side="left")
-    keep = np.arange(n) - first < MAX_DETS
-    order, key_sorted = order[keep], key_sorted[keep]
 
     anns = [(i, a) for i, image_id in enumerate(dataset.ids) for a in dataset.anns_of.get(image_id, ())
             if a["category_id"] in cat_pos]
     gkey = np.array([i * K + cat_pos[a["category_id"]] for i, a in anns], dtype=np.int64)
-    gorder = np.argsort(gkey, kind="stable")   # annotation order inside a pair
-    gkey_sorted = gkey[gorder]
-    gt_box = np.array([a["bbox"] for _, a in anns], dtype=np.float64).reshape(-1, 4)[gorder]
-    gt_area = np.array([a["area"] for _, a in anns], dtype=np.float64)[gorder]
-    gt_crowd = np.array([a.get("iscrowd", 0) for _, a in anns], dtype=np.int32)[gorder]
+    gt_box = np.array([a["bbox"] for _, a in anns], dtype=np.float64).reshape(-1, 4)
+    gt_area = np.array([a["area"] for _, a in anns], dtype=np.float64)
+    gt_crowd = np.array([a.get("iscrowd", 0) for _, a in anns], dtype=np.int32)
 
-    pairs = np.union1d(key_sorted, gkey_sorted)
-    return Packed(categories=categories, pair_key=pairs, det_off=_offsets(key_sorted, pairs),
-                  gt_off=_offsets(gkey_sorted, pairs), det_box=np.ascontiguousarray(box[order]),
-                  det_score=score[order], det_cat=cat[order], gt_box=np.ascontiguousarray(gt_box), gt_area=gt_area,
-                  gt_crowd=gt_crowd)
+    order, gorder, pair_key, det_off, gt_off = pairs.pair_tables(img * K + cat, score, gkey, cut=MAX_DETS)
+    return Packed(categories=categories, pair_key=pair_key, det_off=det_off, gt_off=gt_off,
+                  det_box=np.ascontiguousarray(box[order]), det_score=score[order], det_cat=cat[order],
+                  gt_box=np.ascontiguousarray(gt_box[gorder]), gt_area=gt_area[gorder], gt_crowd=gt_crowd[gorder])
 
 
 def match(packed, device=None):
     """-> (matched uint8 [T, A, Nd], ignored uint8 [T, A, Nd], npig int32 [P, A]) on the device, one launch"""
     from .... import _C
 
-    if device is None:
-        if not torch.cuda.is_available():
-            raise DadetError("box AP matching runs on the HIP device (csrc/coco_match.hip): there is no CPU path")
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = pairs.match_device(device, "box AP matching runs on the HIP device (csrc/coco_match.hip): there is no CPU path")
     up = lambda a: torch.from_numpy(a).to(device)      # noqa: E731
     return _C.coco_match(up(packed.det_box), up(packed.gt_box), up(packed.gt_area), up(packed.gt_crowd), packed.det_off,
                          packed.gt_off, IOU_THRESHOLDS, AREA_RANGES)
@@ -100,19 +83,7 @@ def accumulate(packed, matched, ignored, npig):
     T, A, n = matched.shape
     K = max(len(packed.categories), 1)
     R = len(RECALL_THRESHOLDS)
-    counts = np.bincount(packed.det_cat, minlength=K)
-    L = max(int(counts.max()) if n else 0, 1)
-
-    score = torch.from_numpy(packed.det_score).to(dev)
-    cat = torch.from_numpy(packed.det_cat).to(dev)
-    by_score = torch.sort(score, descending=True, stable=True)[1]      # ties keep image order, then the pair's order
-    by_cat = torch.sort(cat[by_score], stable=True)[1]
-    order = by_score[by_cat]
-    cat_sorted = cat[order]
-    start = torch.from_numpy(np.cumsum(counts) - counts).to(dev)
-    column = torch.arange(n, device=dev) - start[cat_sorted]
-    where = torch.full((K, L), n, dtype=torch.int64, device=dev)        # n = the padding column below
-    where[cat_sorted, column] = order
+    where, _, L = pairs.class_grid(packed.det_score, packed.det_cat, K, dev)      # n = the padding column below
 
     pad = torch.zeros((T * A, 1), dtype=torch.uint8, device=dev)
     m = torch.cat([matched.reshape(T * A, n), pad], 1)[:, where].reshape(T, A, K, L) != 0
@@ -120,8 +91,7 @@ def accumulate(packed, matched, ignored, npig):
     tp = (m & counted).cumsum(-1).to(torch.float64)
     fp = (~m & counted).cumsum(-1).to(torch.float64)
 
-    pair_cat = torch.from_numpy(packed.pair_key % K).to(dev)
-    npig_cat = torch.zeros((K, A), dtype=torch.int64, device=dev).index_add_(0, pair_cat, npig.to(torch.int64))
+    npig_cat = pairs.class_sum(packed.pair_key, K, npig, dev)                     # [K, A]
     has_gt = npig_cat.t() > 0                                                     # [A, K]
     recall = tp / npig_cat.t().clamp(min=1).to(torch.float64)[None, :, :, None]
     precision = tp / (fp + tp + float(np.spacing(1)))

@@ -22,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from ...._lib import DadetError
+from .. import pairs
 
 Packed = collections.namedtuple("Packed", [
     "n_class",        # K = largest label that occurs + 1 (0: no label occurs)
@@ -44,11 +44,6 @@ Curves = collections.namedtuple("Curves", [
     "n_pos",          # int64 numpy [K]: non-difficult ground truths of the class
     "present",        # bool numpy [K]
 ])
-
-
-def _offsets(sorted_keys, pairs):
-    off = np.searchsorted(sorted_keys, pairs, side="left")
-    return np.append(off, len(sorted_keys)).astype(np.int32)
 
 
 def _field(boxlists, name, dtype):
@@ -84,14 +79,10 @@ def pack(pred_boxlists, gt_boxlists):
     present = np.zeros(K, dtype=bool)
     present[label] = True
     present[glabel] = True
-    key, gkey = img * K + label, gimg * K + glabel
-    order = np.lexsort((-score, key))              # stable: equal scores of a pair keep the record order
-    gorder = np.argsort(gkey, kind="stable")       # annotation order inside a pair
-    key_sorted, gkey_sorted = key[order], gkey[gorder]
-    pairs = np.union1d(key_sorted, gkey_sorted)
-    return Packed(n_class=K, present=present, pair_key=pairs, det_off=_offsets(key_sorted, pairs),
-                  gt_off=_offsets(gkey_sorted, pairs), det_box=np.ascontiguousarray(det_box[order]), det_score=score[order],
-                  det_label=label[order], gt_box=np.ascontiguousarray(gt_box[gorder]), gt_difficult=difficult[gorder])
+    order, gorder, pair_key, det_off, gt_off = pairs.pair_tables(img * K + label, score, gimg * K + glabel)
+    return Packed(n_class=K, present=present, pair_key=pair_key, det_off=det_off, gt_off=gt_off,
+                  det_box=np.ascontiguousarray(det_box[order]), det_score=score[order], det_label=label[order],
+                  gt_box=np.ascontiguousarray(gt_box[gorder]), gt_difficult=difficult[gorder])
 
 
 def match(packed, iou_thresholds, device=None):
@@ -99,10 +90,7 @@ def match(packed, iou_thresholds, device=None):
     launch for all thresholds"""
     from .... import _C
 
-    if device is None:
-        if not torch.cuda.is_available():
-            raise DadetError("VOC matching runs on the HIP device (csrc/voc_match.hip): there is no CPU path")
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = pairs.match_device(device, "VOC matching runs on the HIP device (csrc/voc_match.hip): there is no CPU path")
     up = lambda a: torch.from_numpy(a).to(device)      # noqa: E731
     return _C.voc_match(up(packed.det_box), up(packed.gt_box), up(packed.gt_difficult), packed.det_off, packed.gt_off,
                         [float(t) for t in iou_thresholds])
@@ -115,26 +103,13 @@ def accumulate(packed, match, n_pos):
     dev = match.device
     T, n = match.shape
     K = packed.n_class
-    counts = np.bincount(packed.det_label, minlength=K).astype(np.int64)
-    L = max(int(counts.max()) if K else 0, 1)
-
-    score = torch.from_numpy(packed.det_score).to(dev)
-    label = torch.from_numpy(packed.det_label).to(dev)
-    by_score = torch.sort(score, descending=True, stable=True)[1]
-    by_label = torch.sort(label[by_score], stable=True)[1]
-    order = by_score[by_label]
-    label_sorted = label[order]
-    start = torch.from_numpy(np.cumsum(counts) - counts).to(dev)
-    column = torch.arange(n, device=dev) - start[label_sorted]
-    where = torch.full((K, L), n, dtype=torch.int64, device=dev)            # n = the padding column below
-    where[label_sorted, column] = order
+    where, counts, L = pairs.class_grid(packed.det_score, packed.det_label, K, dev)     # n = the padding column below
 
     pad = torch.full((T, 1), -1, dtype=torch.int8, device=dev)
     m = torch.cat([match, pad], 1)[:, where].reshape(T, K, L)
     tp = (m == 1).cumsum(-1).to(torch.float64)
     fp = (m == 0).cumsum(-1).to(torch.float64)
-    pair_label = torch.from_numpy(packed.pair_key % max(K, 1)).to(dev)
-    n_pos_class = torch.zeros(K, dtype=torch.int64, device=dev).index_add_(0, pair_label, n_pos.to(dev).to(torch.int64))
+    n_pos_class = pairs.class_sum(packed.pair_key, K, n_pos, dev)
     prec = tp / (fp + tp)
     rec = tp / n_pos_class.clamp(min=1).to(torch.float64)[None, :, None]
     return Curves(prec=prec, rec=rec, count=counts, n_pos=n_pos_class.cpu().numpy(), present=packed.present)

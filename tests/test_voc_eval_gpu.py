@@ -329,3 +329,52 @@ def test_malformed_offsets_are_refused_before_the_launch():
     assert n_pos.tolist() == [1, 1] and gt_index.tolist() == [0, 0, 0]
     assert match.tolist() == [[1, 0, 1], [1, 0, 1]]          # the exact box takes the ground truth; the half box comes second
     assert iou_max[0].item() == 1.0 and iou_max[2].item() == 1.0
+
+
+def test_both_matchers_share_a_stream():
+    """The two matchers raise the LDS limit per kernel and upload their tables through the same code (csrc/pair_tables.h).  On
+    one stream, in this order: VOC with 81000 B of LDS, a small COCO pair, COCO with a 100 x 150 matrix (120000 B, above the
+    48 KiB a launch gets without asking), a small VOC pair — every output of all four against the plain loops, exactly."""
+    from da_detect_amd.data.evaluation.coco import box_ap
+    from da_detect_amd.data.evaluation.voc import voc_eval
+    from test_coco_eval import ListDataset, _ann, _det, _images, flags_in_packed_order, loop_box_ap
+
+    sixteen = [.3 + .04 * k for k in range(16)]
+    rng = np.random.default_rng(6)
+    voc_big = _crowded(rng, 120, 1000, size=(2048, 1024))
+    voc_small = (pred([[0, 0, 9, 9], [0, 0, 9, 4], [50, 50, 54, 54]], [1, 1, 1], [.9, .8, .7]),
+                 truth([[0, 0, 9, 9], [50, 50, 54, 54]], [1, 1]))
+    coco_small = (ListDataset(_images(1), [_ann(10, 1, [0, 0, 10, 10]), _ann(10, 1, [50, 50, 5, 5])], [1]),
+                  [_det(10, 1, [0, 0, 10, 10], .9), _det(10, 1, [0, 0, 10, 5], .8), _det(10, 1, [50, 50, 5, 5], .7)])
+    gts = [[float(np.round(v, 1)) for v in (rng.uniform(0, 900), rng.uniform(0, 900), side, side * rng.uniform(.6, 1.4))]
+           for side in ([rng.uniform(6, 30), rng.uniform(34, 90), rng.uniform(100, 220)][j % 3] for j in range(150))]
+    dets = []
+    for j in range(100):
+        x, y, w, h = gts[int(rng.integers(150))]
+        s = rng.uniform(.0, .2)
+        box = [x + w * rng.normal(0, s), y + h * rng.normal(0, s), w * (1 + rng.normal(0, s)), h * (1 + rng.normal(0, s))]
+        dets.append(_det(10, 1, [float(np.float32(v)) for v in box], (j + 1) / 128))
+    coco_big = (ListDataset(_images(1), [_ann(10, 1, b, crowd=1 if j % 7 == 6 else 0) for j, b in enumerate(gts)], [1]), dets)
+
+    voc_packed = [voc_eval.pack([p], [g]) for p, g in (voc_big, voc_small)]
+    coco_packed = [box_ap.pack(records, dataset) for dataset, records in (coco_small, coco_big)]
+    assert voc_packed[0].gt_off.tolist() == [0, 1000] and coco_packed[1].det_off.tolist() == [0, 100]
+    assert coco_packed[1].gt_off.tolist() == [0, 150] and coco_packed[0].det_off.tolist() == [0, 3]
+    got = [voc_eval.match(voc_packed[0], sixteen), box_ap.match(coco_packed[0]), box_ap.match(coco_packed[1]),
+           voc_eval.match(voc_packed[1], [.5, .75])]
+    torch.cuda.synchronize()
+
+    for (p, g), thresholds, (match, n_pos, gt_index, iou_max) in ((voc_big, sixteen, got[0]), (voc_small, [.5, .75], got[3])):
+        loop = loop_voc([p], [g], thresholds)
+        assert n_pos.tolist() == loop["n_pos"].tolist()
+        assert torch.equal(iou_max.cpu().view(torch.int32), torch.from_numpy(loop["iou_max"]).view(torch.int32))
+        assert torch.equal(gt_index.cpu(), torch.from_numpy(loop["gt_index"]))
+        assert torch.equal(match.cpu(), torch.from_numpy(loop["match"]))
+    assert got[3][0].tolist() == [[1, 0, 1], [1, 0, 1]] and {-1, 0, 1} <= set(got[0][0].flatten().tolist())
+    for (dataset, records), packed, (matched, ignored, npig) in ((coco_small, coco_packed[0], got[1]),
+                                                                  (coco_big, coco_packed[1], got[2])):
+        want_m, want_i, want_n = flags_in_packed_order(packed, loop_box_ap(records, dataset))
+        assert torch.equal(npig.cpu(), want_n)
+        assert torch.equal(matched.cpu(), want_m) and torch.equal(ignored.cpu(), want_i)
+    assert got[1][0][:, 0, :].tolist() == [[1, 0, 1]] * 10
+    assert 0 < int(got[2][0].sum()) < got[2][0].numel() and 0 < int(got[2][1].sum()) < got[2][1].numel()

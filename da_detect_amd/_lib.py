@@ -70,6 +70,16 @@ class SgdEntry(ctypes.Structure):
                 ("lr", c_float), ("weight_decay", c_float)]
 
 
+class ImageItem(ctypes.Structure):
+    """mirror of dadet_image_item (include/dadet.h)"""
+
+    _fields_ = [(n, c_void_p) for n in ("src", "h_bounds", "h_coeffs", "v_bounds", "v_coeffs")] + [
+        (n, c_int) for n in ("H", "W", "out_h", "out_w", "flip", "h_ksize", "v_ksize", "slot")]
+
+
+IMAGE_BATCH_MAX = 8      # DADET_IMAGE_BATCH_MAX
+
+
 # name -> argtypes ; every function returns int (status) unless listed in _RESTYPES
 _P = c_void_p
 _SIGNATURES = {
@@ -142,6 +152,8 @@ _SIGNATURES = {
     "dadet_image_resample_h": [_P, c_int, c_int, _P, _P, c_int, c_int, _P, _P],
     "dadet_image_resample_v_normalize": [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float),
                                          POINTER(c_float), _P, c_int, _P],
+    "dadet_image_prepare_batch": [POINTER(ImageItem), c_int, c_int, POINTER(c_float), POINTER(c_float), _P, c_int, c_int,
+                                  c_int, _P],
     "dadet_rpn_loss": [_P, _P, _P, _P, c_int, _P, _P, c_int, c_float, _P, _P, _P, _P],
     "dadet_fpn_merge_levels": [POINTER(MergeEntry), c_int, _P],
     "dadet_rpn_loss_rows": [_P, _P, _P, _P, c_int, c_int, _P, c_int, c_float, _P, _P, c_int, _P, _P],

@@ -18,7 +18,8 @@ from ..utils.comm import get_world_size
 from ..utils.imports import load_paths_catalog
 from . import datasets as D
 from . import samplers
-from .collate_batch import BatchCollator, BatchCollator_triplet, BBoxAugCollator
+from .collate_batch import (BatchCollator, BatchCollator_triplet, BBoxAugCollator, RawBatchCollator, RawBatchCollator_triplet,
+                            RawBBoxAugCollator)
 from .datasets import COCODataset, TripletDataset
 from .transforms import build_transforms
 
@@ -183,41 +184,73 @@ def _train_loader(cfg, dataset, is_distributed, start_iter, collator):
                        start_iter, collator)
 
 
-def make_test_data_loader(cfg, dataset, is_distributed=False):
+def _decode_to_tensor(dataset):
+    """switch an already constructed dataset (or every part of a concatenation / triplet) to raw samples"""
+    parts = getattr(dataset, "datasets", None) or [getattr(dataset, n) for n in ("dataset_s", "dataset_p", "dataset_n")
+                                                    if hasattr(dataset, n)]
+    for part in parts:
+        _decode_to_tensor(part)
+    if not parts:
+        dataset.decode_to_tensor = True
+
+
+def _device_prep_loader(cfg, loader, is_train):
+    from .device_prep import DeviceBatchPreparer, DevicePrepLoader
+
+    return DevicePrepLoader(loader, DeviceBatchPreparer(cfg, is_train))
+
+
+def make_test_data_loader(cfg, dataset, is_distributed=False, device_prep=False):
     """evaluation loader over an already constructed dataset (sequential, or sharded by rank when distributed).  With
     cfg.TEST.BBOX_AUG.ENABLED the samples leave it untransformed and unbatched (transforms=None and BBoxAugCollator,
-    build.py:155,168): the dataset's transforms are taken off here, the augmentation passes apply their own."""
-    collator = BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
+    build.py:155,168): the dataset's transforms are taken off here, the augmentation passes apply their own.
+    `device_prep=True`: the dataset hands out decoded pixels (with the decisions of its transforms) and the batches are
+    prepared on the device (data/device_prep.py DevicePrepLoader); under test-time augmentation each image is uploaded
+    once and the passes prepare their inputs from it."""
+    collator = RawBatchCollator() if device_prep else BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
     if cfg.TEST.BBOX_AUG.ENABLED:
         dataset._transforms = None
-        collator = BBoxAugCollator()
-    return _loader_for(cfg, dataset, images_per_gpu(cfg, False), bool(is_distributed), is_distributed, None, 0, collator)
+        collator = RawBBoxAugCollator() if device_prep else BBoxAugCollator()
+    if device_prep:
+        _decode_to_tensor(dataset)
+    loader = _loader_for(cfg, dataset, images_per_gpu(cfg, False), bool(is_distributed), is_distributed, None, 0, collator)
+    return _device_prep_loader(cfg, loader, False) if device_prep else loader
 
 
-def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True):
+def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, decode_to_tensor=False):
     """spec = (ann_file, image_root) for a COCO-style dataset, or ("voc:" + data_dir, split) for one in PASCAL VOC layout
     (the command-line form `voc:DIR,SPLIT` of the tools); the train / test switches are those of `_from_catalog`"""
     first, second = spec
     if first.startswith("voc:"):
         return D.PascalVOCDataset(first[len("voc:"):], second, use_difficult=not is_train, transforms=transforms,
-                                  is_source=is_source)
-    return COCODataset(first, second, remove_images_without_annotations=is_train, transforms=transforms, is_source=is_source)
+                                  is_source=is_source, decode_to_tensor=decode_to_tensor)
+    return COCODataset(first, second, remove_images_without_annotations=is_train, transforms=transforms, is_source=is_source,
+                       decode_to_tensor=decode_to_tensor)
 
 
-def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0):
+def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0, device_prep=False):
     """dataset_specs = {"source": (ann_file, root), "target": (...)[, "auxiliary": (...)]} (or `dataset_from_spec`'s VOC form)
-    -> one loader per domain, iterated jointly by do_da_train (each carrying IMS_PER_BATCH // (2 * num_gpus) images per step)"""
+    -> one loader per domain, iterated jointly by do_da_train (each carrying IMS_PER_BATCH // (2 * num_gpus) images per step).
+    `device_prep=True`: the same batches, prepared on the device from decoded pixels (data/device_prep.py)."""
     tf = build_transforms(cfg, True)
     out = []
     for name in [n for n in ("source", "target", "auxiliary") if n in dataset_specs]:
-        ds = dataset_from_spec(dataset_specs[name], tf, True, name == "source")
-        out.append(_train_loader(cfg, ds, is_distributed, start_iter, BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)))
+        ds = dataset_from_spec(dataset_specs[name], tf, True, name == "source", decode_to_tensor=device_prep)
+        collator = RawBatchCollator() if device_prep else BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
+        loader = _train_loader(cfg, ds, is_distributed, start_iter, collator)
+        out.append(_device_prep_loader(cfg, loader, True) if device_prep else loader)
+    if device_prep:
+        from .device_prep import DevicePrepLoader
+
+        DevicePrepLoader.consumed_jointly(out)
     return out
 
 
-def make_triplet_data_loader(cfg, dataset_specs, is_distributed=False, start_iter=0):
-    """one loader over index-aligned (source, target, auxiliary) samples (build.py:23-63, 332-419)"""
+def make_triplet_data_loader(cfg, dataset_specs, is_distributed=False, start_iter=0, device_prep=False):
+    """one loader over index-aligned (source, target, auxiliary) samples (build.py:23-63, 332-419); `device_prep` as above"""
     tf = build_transforms(cfg, True)
-    ds = [dataset_from_spec(dataset_specs[n], tf, True, n == "source") for n in ("source", "target", "auxiliary")]
-    return _train_loader(cfg, TripletDataset(ds), is_distributed, start_iter,
-                         BatchCollator_triplet(cfg.DATALOADER.SIZE_DIVISIBILITY))
+    ds = [dataset_from_spec(dataset_specs[n], tf, True, n == "source", decode_to_tensor=device_prep)
+          for n in ("source", "target", "auxiliary")]
+    collator = RawBatchCollator_triplet() if device_prep else BatchCollator_triplet(cfg.DATALOADER.SIZE_DIVISIBILITY)
+    loader = _train_loader(cfg, TripletDataset(ds), is_distributed, start_iter, collator)
+    return _device_prep_loader(cfg, loader, True) if device_prep else loader

@@ -39,3 +39,18 @@ class RawBatchCollator(object):
     def __call__(self, batch):
         transposed = list(zip(*batch))
         return list(transposed[0]), list(transposed[1]), list(transposed[2])
+
+
+class RawBatchCollator_triplet(object):
+    """RawBatchCollator for samples of TripletDataset: the nine fields of BatchCollator_triplet in its order, the three
+    image fields as lists of decoded images"""
+
+    def __call__(self, batch):
+        t = list(zip(*batch))
+        return (list(t[0]), t[1], list(t[2]), t[3], list(t[4]), t[5], t[6], t[7], t[8])
+
+
+class RawBBoxAugCollator(BBoxAugCollator):
+    """BBoxAugCollator over a `decode_to_tensor=True` dataset without transforms: the images are uint8 [H,W,3] tensors
+    instead of PIL images (engine/bbox_aug.py selects its device passes by that); a subclass, so that
+    engine.inference still recognises a test-time-augmentation loader by its collator"""

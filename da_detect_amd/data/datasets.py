@@ -2,6 +2,7 @@
 data/datasets/voc.py and data/build.py:23-63 `Dataset_triplet`).  The annotation file is read with the json module (pycocotools /
 torchvision.datasets.CocoDetection are not needed for bounding boxes); segmentation masks and keypoints are outside the
 DA Faster R-CNN path."""
+import collections
 import copy
 import json
 import os
@@ -13,6 +14,22 @@ import torch
 from ..structures.bounding_box import BoxList
 
 MIN_KEYPOINTS_PER_IMAGE = 10
+
+# what a `decode_to_tensor=True` dataset with transforms puts into a sample's image slot: the decoded pixels (uint8 [H,W,3],
+# CPU) and the decisions its transforms WOULD apply, decision = ((out_h, out_w), flip) — data/device_prep.py applies them
+RawImage = collections.namedtuple("RawImage", ["pixels", "decision"])
+
+
+def raw_image(img, transforms):
+    """PIL image -> the image slot of a `decode_to_tensor=True` sample.  The random decisions are drawn here, where the
+    host chain draws them (inside __getitem__, so inside the loader's worker with its seeding) and in its order; with
+    `transforms=None` the slot holds the pixels alone."""
+    pixels = torch.from_numpy(np.array(img, dtype=np.uint8))
+    if transforms is None:
+        return pixels
+    from .transforms import draw_decisions
+
+    return RawImage(pixels, draw_decisions(transforms, img.size))
 
 
 def has_valid_annotation(anno):
@@ -66,7 +83,7 @@ class COCODataset(torch.utils.data.Dataset):
         target.add_field("is_source", torch.full_like(classes, bool(self.is_source), dtype=torch.bool))
         target = target.clip_to_image(remove_empty=True)
         if self.decode_to_tensor:
-            return torch.from_numpy(np.array(img, dtype=np.uint8)), target, idx
+            return raw_image(img, self._transforms), target, idx
         if self._transforms is not None:
             img, target = self._transforms(img, target)
         return img, target, idx
@@ -131,7 +148,7 @@ class PascalVOCDataset(torch.utils.data.Dataset):
         target.add_field("is_source", torch.full_like(labels, bool(self.is_source), dtype=torch.bool))
         target = target.clip_to_image(remove_empty=True)
         if self.decode_to_tensor:
-            return torch.from_numpy(np.array(img, dtype=np.uint8)), target, index
+            return raw_image(img, self._transforms), target, index
         if self._transforms is not None:
             img, target = self._transforms(img, target)
         return img, target, index

@@ -93,6 +93,20 @@ class Normalize(object):
         return (x - shift) / scale, target
 
 
+def draw_decisions(transforms, image_size):
+    """the random decisions `transforms` (a Compose of the steps above) would take for an image of `image_size` = (w, h),
+    drawn from the same stream in the same order — per step, so Resize.get_size before the flip toss — without applying
+    anything: -> ((out_h, out_w), flip).  For the device path (data/device_prep.py), which applies them in its kernel."""
+    w, h = image_size
+    size, flip = (h, w), False
+    for step in getattr(transforms, "transforms", ()):
+        if isinstance(step, Resize):
+            size = step.get_size((size[1], size[0]))
+        elif isinstance(step, RandomHorizontalFlip):
+            flip = step.toss() != flip
+    return (int(size[0]), int(size[1])), bool(flip)
+
+
 def transform_params(cfg, is_train=True):
     """(min_size, max_size, flip_prob) of transforms/build.py:5-14"""
     if is_train:

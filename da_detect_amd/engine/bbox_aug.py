@@ -5,7 +5,11 @@ list of several thousand rows goes through the device filter like any other (csr
 
 The passes build their inputs with this package's own sample transforms (data/transforms.py: Pillow + torch).  The
 configuration is the one the model was built from (`model.cfg`); a model without one — the reference's own tools merge
-into the package-level `cfg` — falls back to that, read at call time."""
+into the package-level `cfg` — falls back to that, read at call time.
+
+Images given as uint8 [H,W,3] tensors (the RawBBoxAugCollator of a `device_prep` loader) instead of PIL images take the
+device path: each image is uploaded once — by the loader, else here — and every pass is one batched preparation launch
+(data/device_prep.py) with that pass's size and flip; no PIL resize and no further upload per pass.  Same bits."""
 import torch
 
 from ..data import transforms as T
@@ -24,6 +28,8 @@ def _cfg_of(model):
 def im_detect_bbox_aug(model, images, device):
     """bbox_aug.py:11-68: identity, flip (H_FLIP), then per scale the plain and (SCALE_H_FLIP) the flipped pass"""
     cfg = _cfg_of(model)
+    if _is_raw(images):
+        images = [image.to(device, non_blocking=True) for image in images]      # once for all passes
     boxlists_ts = [[] for _ in range(len(images))]
 
     def add_preds_t(boxlists_t):
@@ -50,8 +56,24 @@ def im_detect_bbox_aug(model, images, device):
     return [post_processor.filter_results(boxlist, num_classes) for boxlist in merged]
 
 
+def _is_raw(images):
+    return len(images) > 0 and all(isinstance(im, torch.Tensor) and im.dtype == torch.uint8 for im in images)
+
+
+def _detect_raw(model, images, target_scale, target_max_size, device, hflip, cfg):
+    """one pass on decoded uint8 pixels: the pass's (Resize.get_size, flip) for every image, one launch"""
+    from ..data.device_prep import DeviceBatchPreparer
+
+    resize = T.Resize(target_scale, target_max_size)
+    decisions = [(resize.get_size((int(im.shape[1]), int(im.shape[0]))), bool(hflip)) for im in images]
+    batch, _ = DeviceBatchPreparer(cfg, is_train=False)([im.to(device) for im in images], None, decisions)
+    return model(batch)
+
+
 def _detect(model, images, target_scale, target_max_size, device, hflip):
     cfg = _cfg_of(model)
+    if _is_raw(images):
+        return _detect_raw(model, images, target_scale, target_max_size, device, hflip, cfg)
     steps = [T.Resize(target_scale, target_max_size)]
     if hflip:
         steps.append(T.RandomHorizontalFlip(1.0))

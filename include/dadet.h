@@ -486,6 +486,25 @@ int dadet_image_resample_v_normalize(const unsigned char* image_hwc, int in_h, i
                                      const float* mean3, const float* std3, float* out_hw3, int out_row_stride,
                                      void* stream);
 
+/* The same chain for a whole batch in ONE launch, the padding included.  items: HOST array of n <= DADET_IMAGE_BATCH_MAX
+ * descriptors (they travel by value in the kernel arguments: nothing of them needs to outlive the call); tables and
+ * pixels are device memory, h_bounds NULL when out_w == W and v_bounds NULL when out_h == H (Pillow skips that pass).
+ * out: fp32 [n_slots][Hp][Wp][3]; every pixel of the slots named by the items is written — the image (mirrored when
+ * flip) inside [out_h][out_w], zeros beyond — so the caller need not clear it.  Both passes run in one workgroup per
+ * 16 x 64 output tile with the horizontal pass's 8-bit rows held in LDS, walked in chunks of 64 input rows: one chunk
+ * up to a vertical factor H / out_h of 3, more above it, with the same bits.  mean3 / std3 are HOST pointers. */
+#define DADET_IMAGE_BATCH_MAX 8
+typedef struct dadet_image_item {
+  const void* src;        /* uint8 [H][W][3] RGB */
+  const void* h_bounds;   /* int32 [out_w][2] or NULL */
+  const void* h_coeffs;   /* int32 [out_w][h_ksize] */
+  const void* v_bounds;   /* int32 [out_h][2] or NULL */
+  const void* v_coeffs;   /* int32 [out_h][v_ksize] */
+  int H, W, out_h, out_w, flip, h_ksize, v_ksize, slot;
+} dadet_image_item;
+int dadet_image_prepare_batch(const dadet_image_item* items, int n, int to_bgr255, const float* mean3,
+                              const float* std3, float* out, int n_slots, int Hp, int Wp, void* stream);
+
 /* Fused detection losses: value and gradient in one single-workgroup launch (losses.hip).
  * dadet_rpn_loss replaces RPNLossComputation.__call__'s loss part (modeling/rpn/loss.py:125-143): objectness /
  * box_regression are the flattened NHWC prediction maps ([N*H*W*A] and [N*H*W*A][4], the order of

@@ -23,7 +23,10 @@ overrides (the evaluation pass itself then already logs the recalls: engine/infe
 domain-adaptation papers report, and writes `result.txt`.  `--dataset voc:DIR,SPLIT` names a set in PASCAL VOC layout; it has
 no COCO form, so it is always scored VOC-style (`--metric coco` is then read as voc07, the reference's default), and with
 `--config-file` its evaluation pass runs in this process (one GPU) and leaves `predictions.pth` in
-`<output-dir>/inference/<DIR's name>_<SPLIT>/`: tools/test_net_da.py takes COCO-format sets only."""
+`<output-dir>/inference/<DIR's name>_<SPLIT>/`: tools/test_net_da.py takes COCO-format sets only.
+
+`--device-prep` (with `--config-file`): the evaluation pass runs in this process as well, for either kind of set, fed from the
+device input pipeline — test-time augmentation through `TEST.BBOX_AUG.ENABLED True` included."""
 import argparse
 import logging
 import os
@@ -45,9 +48,10 @@ def _pair(text):
     return ann, root
 
 
-def _voc_evaluation_pass(args, folder):
-    """the evaluation pass over a VOC-layout set, in this process (tools/test_net_da.py builds COCO records, which such a set
-    has no ids for): detector, weights, test loader, engine.inference — it leaves predictions.pth in `folder`"""
+def _evaluation_pass(args, folder):
+    """the evaluation pass in this process — over a VOC-layout set (tools/test_net_da.py builds COCO records, which such a
+    set has no ids for), or over any set with --device-prep (tools/test_net_da.py feeds from the host transforms only):
+    detector, weights, test loader, engine.inference — it leaves predictions.pth in `folder`"""
     from da_detect_amd.config import cfg
     from da_detect_amd.data.build import make_test_data_loader
     from da_detect_amd.data.transforms import build_transforms
@@ -67,8 +71,9 @@ def _voc_evaluation_pass(args, folder):
     model.eval()
     dataset = dataset_from_spec(args.dataset, build_transforms(c, is_train=False), is_train=False)
     os.makedirs(folder, exist_ok=True)
-    inference(model, make_test_data_loader(c, dataset), dataset_name=",".join(args.dataset), box_only=c.MODEL.RPN_ONLY,
-              device=device, output_folder=folder, evaluate=lambda **_: None)      # scored below, from the saved file
+    inference(model, make_test_data_loader(c, dataset, device_prep=args.device_prep), dataset_name=",".join(args.dataset),
+              box_only=c.MODEL.RPN_ONLY, device=device, output_folder=folder,
+              evaluate=lambda **_: None)      # scored below, from the saved file
 
 
 def main():
@@ -84,6 +89,10 @@ def main():
     ap.add_argument("--metric", choices=("coco", "voc07", "voc12"), default="coco",
                     help="coco: COCO box AP (default); voc07 / voc12: PASCAL VOC AP, 11-point / area metric")
     ap.add_argument("--voc-iou", type=float, nargs="+", default=[0.5], help="IoU threshold(s) of the VOC metrics")
+    ap.add_argument("--device-prep", action="store_true",
+                    help="with --config-file: the evaluation pass runs in this process (one GPU) and prepares its batches — and, "
+                         "with TEST.BBOX_AUG.ENABLED True, every augmentation pass — on the device from decoded uint8 pixels "
+                         "(data/device_prep.py); same inputs as the host transforms, bit for bit")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE overrides of the yaml (with --config-file)")
     args = ap.parse_args()
     if (args.predictions is None) == (args.config_file is None):
@@ -96,8 +105,8 @@ def main():
         name = os.path.basename(args.dataset[0][len("voc:"):].rstrip("/")) + "_" + args.dataset[1] if voc else \
             os.path.splitext(os.path.basename(args.dataset[0]))[0]
         folder = os.path.join(args.output_dir, "inference", name)
-        if voc:
-            _voc_evaluation_pass(args, folder)
+        if voc or args.device_prep:
+            _evaluation_pass(args, folder)
         else:
             run = [sys.executable, os.path.join(ROOT, "tools", "test_net_da.py"), "--config-file", args.config_file, "--dataset",
                    ",".join(args.dataset), "--output-dir", args.output_dir] + (["--ckpt", args.ckpt] if args.ckpt else []) + args.opts

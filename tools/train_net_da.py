@@ -61,6 +61,10 @@ def main():
                     help="MODEL.WEIGHT is a checkpoint of THIS run: restore optimizer / scheduler state too and shorten "
                          "the loaders by its iteration (default: fine-tune — weights only, full schedule, as the "
                          "reference fork does with its optimizer restore commented out)")
+    ap.add_argument("--device-prep", action="store_true",
+                    help="feed the loop from the device input pipeline: the loaders hand over decoded uint8 pixels, resize / "
+                         "flip / normalise / pad run in one launch per batch on a side stream (data/device_prep.py); same "
+                         "batches as the host transforms, bit for bit")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE overrides of the yaml")
     args = ap.parse_args()
 
@@ -143,9 +147,10 @@ def main():
         # train_net_triplet.py:123-134: ALIGNMENT pools the three domains with the TARGET image's proposals, which is
         # only meaningful for index-aligned renderings of one scene -> ONE loader over aligned triplets
         source = negative = []
-        positive = make_triplet_data_loader(cfg, specs, is_distributed=world > 1, start_iter=start)
+        positive = make_triplet_data_loader(cfg, specs, is_distributed=world > 1, start_iter=start,
+                                            device_prep=args.device_prep)
     else:
-        loaders = make_da_data_loaders(cfg, specs, is_distributed=world > 1, start_iter=start)
+        loaders = make_da_data_loaders(cfg, specs, is_distributed=world > 1, start_iter=start, device_prep=args.device_prep)
         source, positive = loaders[0], loaders[1]
         negative = loaders[2] if triplet else []
     do_da_train(model, source, positive, negative, None, optimizer, scheduler, checkpointer, device,

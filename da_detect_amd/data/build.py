@@ -217,10 +217,26 @@ def make_test_data_loader(cfg, dataset, is_distributed=False, device_prep=False)
     return _device_prep_loader(cfg, loader, False) if device_prep else loader
 
 
-def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, decode_to_tensor=False):
+RAIN_PREFIX = "rain:"
+
+
+def is_rain_spec(spec):
+    return spec[0].startswith(RAIN_PREFIX)
+
+
+def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, decode_to_tensor=False, source_spec=None):
     """spec = (ann_file, image_root) for a COCO-style dataset, or ("voc:" + data_dir, split) for one in PASCAL VOC layout
-    (the command-line form `voc:DIR,SPLIT` of the tools); the train / test switches are those of `_from_catalog`"""
+    (the command-line form `voc:DIR,SPLIT` of the tools); the train / test switches are those of `_from_catalog`.
+    ("rain:" + mask_dir, "") — the tools' `rain:MASKDIR` — is the rainy rendering of `source_spec`'s images, synthesised per
+    sample from the rain masks of that folder (datasets.RainyDataset, data/rain.py); never a source domain."""
     first, second = spec
+    if first.startswith(RAIN_PREFIX):
+        from .rain import RainMasks
+
+        if source_spec is None or is_rain_spec(source_spec):
+            raise ValueError("a rain:MASKDIR dataset is built over the source dataset: source_spec is missing")
+        inner = dataset_from_spec(source_spec, transforms, is_train, False, decode_to_tensor)
+        return D.RainyDataset(inner, RainMasks(first[len(RAIN_PREFIX):]))
     if first.startswith("voc:"):
         return D.PascalVOCDataset(first[len("voc:"):], second, use_difficult=not is_train, transforms=transforms,
                                   is_source=is_source, decode_to_tensor=decode_to_tensor)
@@ -229,13 +245,15 @@ def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, deco
 
 
 def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0, device_prep=False):
-    """dataset_specs = {"source": (ann_file, root), "target": (...)[, "auxiliary": (...)]} (or `dataset_from_spec`'s VOC form)
+    """dataset_specs = {"source": (ann_file, root), "target": (...)[, "auxiliary": (...)]} (or `dataset_from_spec`'s VOC form;
+    "auxiliary" may be ("rain:" + mask_dir, ""): the source images under synthesised rain)
     -> one loader per domain, iterated jointly by do_da_train (each carrying IMS_PER_BATCH // (2 * num_gpus) images per step).
     `device_prep=True`: the same batches, prepared on the device from decoded pixels (data/device_prep.py)."""
     tf = build_transforms(cfg, True)
     out = []
     for name in [n for n in ("source", "target", "auxiliary") if n in dataset_specs]:
-        ds = dataset_from_spec(dataset_specs[name], tf, True, name == "source", decode_to_tensor=device_prep)
+        ds = dataset_from_spec(dataset_specs[name], tf, True, name == "source", decode_to_tensor=device_prep,
+                               source_spec=dataset_specs["source"])
         collator = RawBatchCollator() if device_prep else BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)
         loader = _train_loader(cfg, ds, is_distributed, start_iter, collator)
         out.append(_device_prep_loader(cfg, loader, True) if device_prep else loader)
@@ -247,10 +265,20 @@ def make_da_data_loaders(cfg, dataset_specs, is_distributed=False, start_iter=0,
 
 
 def make_triplet_data_loader(cfg, dataset_specs, is_distributed=False, start_iter=0, device_prep=False):
-    """one loader over index-aligned (source, target, auxiliary) samples (build.py:23-63, 332-419); `device_prep` as above"""
+    """one loader over index-aligned (source, target, auxiliary) samples (build.py:23-63, 332-419); `device_prep` as above.
+    A `rain:MASKDIR` auxiliary is built over the source dataset OBJECT: the triplet decodes the source image once and, under
+    `device_prep`, uploads it once."""
     tf = build_transforms(cfg, True)
     ds = [dataset_from_spec(dataset_specs[n], tf, True, n == "source", decode_to_tensor=device_prep)
-          for n in ("source", "target", "auxiliary")]
+          for n in ("source", "target")]
+    if is_rain_spec(dataset_specs["auxiliary"]):
+        from .rain import RainMasks
+
+        ds.append(D.RainyDataset(ds[0], RainMasks(dataset_specs["auxiliary"][0][len(RAIN_PREFIX):])))
+        triplet = D.RainTripletDataset(ds)
+    else:
+        ds.append(dataset_from_spec(dataset_specs["auxiliary"], tf, True, False, decode_to_tensor=device_prep))
+        triplet = TripletDataset(ds)
     collator = RawBatchCollator_triplet() if device_prep else BatchCollator_triplet(cfg.DATALOADER.SIZE_DIVISIBILITY)
-    loader = _train_loader(cfg, TripletDataset(ds), is_distributed, start_iter, collator)
+    loader = _train_loader(cfg, triplet, is_distributed, start_iter, collator)
     return _device_prep_loader(cfg, loader, True) if device_prep else loader

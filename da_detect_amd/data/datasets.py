@@ -233,3 +233,112 @@ class TripletDataset(torch.utils.data.Dataset):
 
 
 Dataset_triplet = TripletDataset      # the reference's name (data/build.py:23)
+
+
+# ------------------------------------------------------------------------------- the synthesised rainy domain (data/rain.py)
+class RainImage(RawImage):
+    """the image slot of a `decode_to_tensor=True` sample of RainyDataset: a RawImage of the SOURCE pixels that also says
+    which rain mask to blend into them and how (data/rain.py RainPlan) — data/device_prep.py synthesises the rainy image on
+    the device before it prepares the batch.  In an aligned triplet `pixels` is the source sample's own tensor."""
+
+    def __new__(cls, pixels, decision, mask_index, plan):
+        self = super(RainImage, cls).__new__(cls, pixels, decision)
+        self.mask_index, self.plan = mask_index, plan
+        return self
+
+    def __reduce__(self):
+        return RainImage, (self.pixels, self.decision, self.mask_index, self.plan)
+
+
+def finish_sample(dataset, img, target, index):
+    """what COCODataset / PascalVOCDataset.__getitem__ do with a loaded (PIL image, target): a raw sample, or its transforms"""
+    if dataset.decode_to_tensor:
+        return raw_image(img, dataset._transforms), target, index
+    if dataset._transforms is not None:
+        img, target = dataset._transforms(img, target)
+    return img, target, index
+
+
+class RainyDataset(torch.utils.data.Dataset):
+    """the rainy rendering of `source`'s images, synthesised per sample instead of read from disk (data/rain.py): same
+    length, annotations and get_img_info, is_source False.  Every sample draws, from Python's `random` and before the
+    decisions of its transforms: the rain mask (randrange) and the seed (getrandbits(32)) of the numpy RandomState its rain
+    plan comes from — so every epoch sees fresh rain.  Host chain: the composited PIL image goes through the source's
+    transforms.  decode_to_tensor: the image slot is a RainImage (source pixels + mask index + plan + decisions).
+    `source` is a COCODataset / PascalVOCDataset; its transforms and decode_to_tensor switch are this dataset's.  The
+    untransformed samples come from a shallow copy of it without transforms (`load`)."""
+
+    is_source = False
+
+    def __init__(self, source, masks):
+        self.source, self.masks = source, masks
+        self._plain = copy.copy(source)
+        self._plain._transforms, self._plain.decode_to_tensor = None, False
+
+    _transforms = property(lambda self: self.source._transforms,
+                           lambda self, value: setattr(self.source, "_transforms", value))
+    decode_to_tensor = property(lambda self: self.source.decode_to_tensor,
+                                lambda self, value: setattr(self.source, "decode_to_tensor", value))
+
+    def __len__(self):
+        return len(self.source)
+
+    def get_img_info(self, index):
+        return self.source.get_img_info(index)
+
+    def __getattr__(self, name):            # id maps, category tables, get_groundtruth: the source's
+        if name in ("source", "masks", "_plain") or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.source, name)
+
+    def load(self, index):
+        """-> (PIL image, target) of the source sample, before any transform, the domain flag still the source's"""
+        img, target, _ = self._plain[index]
+        return img, target
+
+    def rainy_sample(self, img, target, index, pixels=None):
+        """img, target: `load(index)` (neither is modified); pixels: img as a uint8 tensor when the caller has it already
+        (the aligned triplet's source sample)"""
+        import random
+
+        from . import rain
+        from .transforms import draw_decisions
+
+        mask_index = random.randrange(len(self.masks))
+        plan = rain.draw_rain_plan(np.random.RandomState(random.getrandbits(32)), img.size[0], img.size[1])
+        target = copy.deepcopy(target)
+        target.add_field("is_source", torch.zeros_like(target.get_field("labels"), dtype=torch.bool))
+        if self.decode_to_tensor:
+            if pixels is None:
+                pixels = torch.from_numpy(np.array(img, dtype=np.uint8))
+            return RainImage(pixels, draw_decisions(self._transforms, img.size), mask_index, plan), target, index
+        from PIL import Image
+
+        img = Image.fromarray(rain.synthesize_host(np.asarray(img, dtype=np.uint8), self.masks.host_mask(mask_index, img.size),
+                                                   plan))
+        if self._transforms is not None:
+            img, target = self._transforms(img, target)
+        return img, target, index
+
+    def __getitem__(self, index):
+        img, target = self.load(index)
+        return self.rainy_sample(img, target, index)
+
+
+class RainTripletDataset(TripletDataset):
+    """TripletDataset whose auxiliary is a RainyDataset over the source dataset ITSELF: the source image is decoded once per
+    triplet — the source sample is finished from it, the rainy sample drawn from it after the target sample, where a third
+    dataset's sample would draw; as raw samples the two share one pixel tensor (one upload)."""
+
+    def __init__(self, datasets):
+        super(RainTripletDataset, self).__init__(datasets)
+        assert isinstance(self.dataset_n, RainyDataset) and self.dataset_n.source is self.dataset_s
+
+    def __getitem__(self, index):
+        decoded, plain = self.dataset_n.load(index)
+        img_s, target_s, i1 = finish_sample(self.dataset_s, decoded, plain, index)
+        img_p, target_p, i2 = self.dataset_p[index]
+        img_n, target_n, i3 = self.dataset_n.rainy_sample(decoded, plain, index,
+                                                          img_s.pixels if isinstance(img_s, RawImage) else None)
+        return (img_s, target_s, img_p, self._with_domain(target_s, target_p), img_n,
+                self._with_domain(target_s, target_n), i1, i2, i3)

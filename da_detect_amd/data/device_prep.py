@@ -17,7 +17,7 @@ import torch
 
 from .. import _lib
 from ..structures.image_list import ImageList
-from .datasets import RawImage
+from .datasets import RainImage, RainyDataset, RawImage
 from .transforms import RandomHorizontalFlip, Resize, transform_params
 
 _PRECISION_BITS = 32 - 8 - 2
@@ -207,7 +207,11 @@ class DevicePrepLoader(object):
     for the batch's event when it receives it.  Two staging buffers take turns, each reused only after the upload that
     read it has finished (its event); the device tensors are allocated on the side stream and registered with the
     consumer's stream at the hand-over (record_stream), so the allocator does not recycle them while either stream may
-    still use them.  Loaders read side by side are joined with `consumed_jointly`."""
+    still use them.  Loaders read side by side are joined with `consumed_jointly`.
+
+    Samples of a RainyDataset (`RainImage`: source pixels + rain mask index + plan) become their rainy image on the side
+    stream before the preparation launch (data/rain.py synthesize_device); pixels two samples share — an aligned triplet's
+    source and rainy sample — are copied and uploaded once."""
 
     SIDE_STREAM = 3            # utils/streams.py: 0 / 1 bookkeeping sections, 2 the weight-gradient lane
 
@@ -274,15 +278,19 @@ class DevicePrepLoader(object):
         """every image of the batch through ONE pinned buffer and ONE copy -> per-image device views (same kind as given:
         RawImage or bare pixels)"""
         pixels = [im.pixels if isinstance(im, RawImage) else im for im in images]
-        offsets, total = [], 0
+        offsets, total, seen = [], 0, {}
         for p in pixels:
             assert p.dtype == torch.uint8 and p.dim() == 3 and p.shape[2] == 3 and not p.is_cuda
-            offsets.append(total)
-            total += (p.numel() + 255) // 256 * 256
+            # an aligned triplet's rainy sample carries the source sample's own tensor: one copy, one upload, two views
+            key = (p.data_ptr(), tuple(p.shape), p.stride())
+            if key not in seen:
+                seen[key] = total
+                total += (p.numel() + 255) // 256 * 256
+            offsets.append(seen[key])
         stage = self._staging[self._turn]
         self._turn ^= 1
         host = stage.take(total)
-        for p, off in zip(pixels, offsets):
+        for off, p in {off: p for p, off in zip(pixels, offsets)}.items():
             host[off:off + p.numel()].view(p.shape).copy_(p)
         with torch.cuda.stream(side):
             dev = host[:total].to(self.device, non_blocking=True)
@@ -290,16 +298,34 @@ class DevicePrepLoader(object):
         views = [dev[off:off + p.numel()].view(p.shape) for p, off in zip(pixels, offsets)]
         return [RawImage(v, im.decision) if isinstance(im, RawImage) else v for v, im in zip(views, images)]
 
+    def _rain_masks(self):
+        dataset = self.loader.dataset
+        for part in (dataset, getattr(dataset, "dataset_n", None)):
+            if isinstance(part, RainyDataset):
+                return part.masks
+        raise _lib.DadetError("a rainy sample arrived from a loader without a RainyDataset")
+
+    def _rain(self, sample, uploaded):
+        """a RainyDataset sample whose SOURCE pixels are on the device -> RawImage of the rainy image, synthesised on the
+        current (side) stream (data/rain.py synthesize_device); the mask comes from the masks' device cache"""
+        from .rain import synthesize_device
+
+        H, W = int(uploaded.pixels.shape[0]), int(uploaded.pixels.shape[1])
+        mask = self._rain_masks().device_mask(sample.mask_index, (W, H), self.device)
+        return RawImage(synthesize_device(uploaded.pixels, mask, sample.plan), uploaded.decision)
+
     def _stage(self, raw):
         from ..utils.streams import side_stream
 
         side = side_stream(self.device, self.SIDE_STREAM)
         groups = (0,) if len(raw) == 3 else (0, 2, 4)             # (images, targets) field pairs of the batch
         counts = [len(raw[g]) for g in groups]
-        uploaded = self._upload([im for g in groups for im in raw[g]], side)
+        flat = [im for g in groups for im in raw[g]]
+        uploaded = self._upload(flat, side)
         out = list(raw)
         source_decisions = None
         with torch.cuda.stream(side):
+            uploaded = [self._rain(im, up) if isinstance(im, RainImage) else up for im, up in zip(flat, uploaded)]
             for g, first in zip(groups, np.cumsum([0] + counts[:-1])):
                 images = uploaded[first:first + len(raw[g])]
                 if not all(isinstance(im, RawImage) for im in images):

@@ -505,6 +505,27 @@ typedef struct dadet_image_item {
 int dadet_image_prepare_batch(const dadet_image_item* items, int n, int to_bgr255, const float* mean3,
                               const float* std3, float* out, int n_slots, int Hp, int Wp, void* stream);
 
+/* Rain synthesis (rain.hip): the auxiliary rainy rendering of a source image from a rain-mask image, replacing the reference's
+ * offline efficientderain-master/generate_rainy_cityscape.py (rain_aug -> augment_and_mix(severity 3, width 3) -> Pillow affine
+ * warps -> screen blend -> 8-bit image).  image_hwc / mask_hwc / out_hwc: uint8 [H][W][3] RGB, device memory, the mask
+ * already at the image's size.  The drawn plan comes from the host (da_detect_amd/data/rain.py): coeffs HOST double
+ * [DADET_RAIN_CHAINS][depth][6], the data Pillow's Image.transform(size, AFFINE, data, BILINEAR) receives per operator; ws3
+ * HOST float[3] the chain weights; c0 = max(1 - m, 0.7), c1 = max(m, 0.5 / max(ws)) as fp32.  Per pixel:
+ *   u_i = chain i's warps of the mask (float64 bilinear, 0 outside, truncated to 8 bits after every warp)
+ *   mix = f32(f64(mix) + f64(ws_i) * (u_i / 255.)) for i = 0, 1, 2;   R = f32(c0 * (f32(mask) / 255)) + f32(c1 * mix)
+ *   out = saturate_u8(round_half_even(((img + R) - img * R) * 255)),  img = f32(image) / 255
+ * depth - 1 warp launches (the three chains in one launch, 8 bit -> 8 bit through `scratch`) and one final launch that
+ * evaluates the last warp of every chain on the fly: no float image is written.  scratch: device memory of at least
+ * dadet_rain_scratch_bytes(H, W, depth) bytes (0 for depth 1), 4-byte aligned like out_hwc; its content before and after
+ * the call is meaningless. */
+#define DADET_RAIN_CHAINS 3
+#define DADET_RAIN_MAX_DEPTH 8
+#define DADET_RAIN_MAX_PIXELS (1 << 28)
+int dadet_rain_scratch_bytes(int H, int W, int depth, size_t* bytes);
+int dadet_rain_synthesize(const unsigned char* image_hwc, const unsigned char* mask_hwc, int H, int W, int depth,
+                          const double* coeffs, const float* ws3, float c0, float c1, unsigned char* out_hwc,
+                          void* scratch, size_t scratch_bytes, void* stream);
+
 /* Fused detection losses: value and gradient in one single-workgroup launch (losses.hip).
  * dadet_rpn_loss replaces RPNLossComputation.__call__'s loss part (modeling/rpn/loss.py:125-143): objectness /
  * box_regression are the flattened NHWC prediction maps ([N*H*W*A] and [N*H*W*A][4], the order of

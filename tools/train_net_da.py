@@ -4,7 +4,7 @@ detector, the per-tensor SGD groups, the cosine schedule, the checkpointer, the 
 then engine.trainer.do_da_train.  One process per GPU:
 
     python tools/train_net_da.py --config-file configs/da_faster_rcnn/<yaml> \\
-        --source ann.json,imgdir --target ann.json,imgdir [--auxiliary ann.json,imgdir] [KEY VALUE ...]
+        --source ann.json,imgdir --target ann.json,imgdir [--auxiliary ann.json,imgdir | rain:MASKDIR] [KEY VALUE ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/train_net_da.py ...
     python tools/train_net_da.py --config-file <yaml> --synthetic 20        # no dataset: 20 seeded synthetic steps
 
@@ -45,6 +45,8 @@ def setup_seed(seed):
 
 
 def _pair(text):
+    if text.startswith("rain:"):        # --auxiliary rain:MASKDIR: the source images under synthesised rain (data/rain.py)
+        return text, ""
     ann, root = text.split(",")
     return ann, root
 
@@ -55,7 +57,10 @@ def main():
     ap.add_argument("--source", type=_pair, help="ann.json,imgdir — or voc:DIR,SPLIT for a dataset in PASCAL VOC layout "
                                                  "(likewise --target and --auxiliary)")
     ap.add_argument("--target", type=_pair)
-    ap.add_argument("--auxiliary", type=_pair)
+    ap.add_argument("--auxiliary", type=_pair,
+                    help="ann.json,imgdir of the rainy renderings — or rain:MASKDIR to synthesise them per sample from the "
+                         "source images and the rain-mask images of MASKDIR (fresh rain every epoch; on the device under "
+                         "--device-prep)")
     ap.add_argument("--synthetic", type=int, default=0, help="run N steps on seeded synthetic batches instead of datasets")
     ap.add_argument("--resume", action="store_true",
                     help="MODEL.WEIGHT is a checkpoint of THIS run: restore optimizer / scheduler state too and shorten "

@@ -157,6 +157,9 @@ _SIGNATURES = {
     "dadet_rain_scratch_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
     "dadet_rain_synthesize": [_P, _P, c_int, c_int, c_int, POINTER(ctypes.c_double), POINTER(c_float), c_float, c_float, _P, _P,
                               c_size_t, _P],
+    "dadet_instance_boxes_workspace_bytes": [c_int, POINTER(c_size_t)],
+    "dadet_instance_boxes": [_P, ctypes.c_longlong, POINTER(c_int), POINTER(ctypes.c_longlong), c_int, _P, _P, _P, c_size_t,
+                             _P],
     "dadet_rpn_loss": [_P, _P, _P, _P, c_int, _P, _P, c_int, c_float, _P, _P, _P, _P],
     "dadet_fpn_merge_levels": [POINTER(MergeEntry), c_int, _P],
     "dadet_rpn_loss_rows": [_P, _P, _P, _P, c_int, c_int, _P, c_int, c_float, _P, _P, c_int, _P, _P],

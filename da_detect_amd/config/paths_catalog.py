@@ -70,9 +70,27 @@ class DatasetCatalog(object):
             raise ValueError('a VOC-layout dataset name must contain "voc" and not "coco", got {!r}'.format(name))
         cls.DATASETS[name] = {"data_dir": data_dir, "split": split}
 
+    @classmethod
+    def register_cityscapes(cls, name, root, split, variant="plain", beta=0.02, car_only=False, device=None):
+        """add / replace an entry for Cityscapes as unpacked from its archives (`root` holds gtFine/<split>/<city>/ and
+        leftImg8bit[_foggy|_rain]/<split>/...): the boxes are built from the instance-id maps when the dataset is
+        (data/cityscapes.py), no converted json is needed.  variant: "plain", "foggy" (with beta 0.02, 0.01 or 0.005) or
+        "rain".  device: where the boxes are computed (None: the HIP device when there is one, else the host; "cpu").  Such an
+        entry is recognised by what it holds, whatever its name."""
+        if variant not in ("plain", "foggy", "rain"):
+            raise ValueError('variant must be "plain", "foggy" or "rain", got {!r}'.format(variant))
+        cls.DATASETS[name] = {"cityscapes_root": root, "split": split, "variant": variant, "beta": beta, "car_only": car_only,
+                              "device": device}
+
     @staticmethod
     def get(name):
-        if "coco" in name:      # every name above contains "coco" (".._cocostyle"), the reference's dispatch rule
+        if "cityscapes_root" in DatasetCatalog.DATASETS.get(name, ()):
+            attrs = DatasetCatalog.DATASETS[name]
+            data_dir = os.environ.get("DADET_DATA_DIR", DatasetCatalog.DATA_DIR)
+            return dict(factory="CityscapesDataset", args=dict(
+                root=os.path.join(data_dir, attrs["cityscapes_root"]), split=attrs["split"], variant=attrs["variant"],
+                beta=attrs["beta"], car_only=attrs["car_only"], device=attrs["device"]))
+        if "coco" in name:     # every name above contains "coco" (".._cocostyle"), the reference's dispatch rule
             if name not in DatasetCatalog.DATASETS:
                 raise RuntimeError("Dataset not available: {}".format(name))
             attrs = DatasetCatalog.DATASETS[name]

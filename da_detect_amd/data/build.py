@@ -85,9 +85,12 @@ def _catalog(cfg):
 def _from_catalog(name, catalog, transforms, is_train, is_source):
     """one dataset from its catalog entry (build.py:84-103, 141-169)"""
     data = catalog.get(name)
-    factory = getattr(D, data["factory"])
+    if data["factory"] == "CityscapesDataset":
+        from .cityscapes import CityscapesDataset as factory
+    else:
+        factory = getattr(D, data["factory"])
     args = dict(data["args"])
-    if data["factory"] == "COCODataset":
+    if data["factory"] in ("COCODataset", "CityscapesDataset"):
         args["remove_images_without_annotations"] = is_train
     if data["factory"] == "PascalVOCDataset":
         args["use_difficult"] = not is_train
@@ -218,18 +221,44 @@ def make_test_data_loader(cfg, dataset, is_distributed=False, device_prep=False)
 
 
 RAIN_PREFIX = "rain:"
+CITYSCAPES_PREFIX = "cityscapes:"
+
+
+def parse_dataset_spec(text):
+    """a tool's dataset argument -> the (first, second) pair `dataset_from_spec` takes: `ann.json,imgdir`, `voc:DIR,SPLIT`,
+    `rain:MASKDIR` (second = "") or `cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly]` (second keeps the options)"""
+    if text.startswith(RAIN_PREFIX):
+        return text, ""
+    if text.startswith(CITYSCAPES_PREFIX):
+        first, second = text.split(",", 1)
+        from .cityscapes import parse_options
+
+        parse_options(second)
+        return first, second
+    first, second = text.split(",")
+    return first, second
 
 
 def is_rain_spec(spec):
     return spec[0].startswith(RAIN_PREFIX)
 
 
-def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, decode_to_tensor=False, source_spec=None):
+def dataset_from_spec(spec, transforms=None, is_train=True, is_source=True, decode_to_tensor=False, source_spec=None,
+                      device=None):
     """spec = (ann_file, image_root) for a COCO-style dataset, or ("voc:" + data_dir, split) for one in PASCAL VOC layout
     (the command-line form `voc:DIR,SPLIT` of the tools); the train / test switches are those of `_from_catalog`.
     ("rain:" + mask_dir, "") — the tools' `rain:MASKDIR` — is the rainy rendering of `source_spec`'s images, synthesised per
-    sample from the rain masks of that folder (datasets.RainyDataset, data/rain.py); never a source domain."""
+    sample from the rain masks of that folder (datasets.RainyDataset, data/rain.py); never a source domain.
+    ("cityscapes:" + root, "SPLIT[,foggy[=BETA]|rain][,caronly]") — the tools' `cityscapes:ROOT,SPLIT[,...]` — is Cityscapes as
+    unpacked from its archives, the boxes taken from the instance-id maps (data/cityscapes.py); `device` is where such a set
+    computes them (None: the HIP device when there is one, else the host; "cpu"), and means nothing to the other kinds."""
     first, second = spec
+    if first.startswith(CITYSCAPES_PREFIX):
+        from .cityscapes import CityscapesDataset, parse_options
+
+        return CityscapesDataset(first[len(CITYSCAPES_PREFIX):], remove_images_without_annotations=is_train,
+                                 transforms=transforms, is_source=is_source, decode_to_tensor=decode_to_tensor,
+                                 device=device, **parse_options(second))
     if first.startswith(RAIN_PREFIX):
         from .rain import RainMasks
 

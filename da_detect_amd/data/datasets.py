@@ -44,8 +44,11 @@ def has_valid_annotation(anno):
 class COCODataset(torch.utils.data.Dataset):
     def __init__(self, ann_file, root, remove_images_without_annotations, transforms=None, is_source=True,
                  decode_to_tensor=False):
-        with open(ann_file) as f:
-            data = json.load(f)
+        if isinstance(ann_file, dict):               # already loaded (data/cityscapes.py builds it from the id maps)
+            data = ann_file
+        else:
+            with open(ann_file) as f:
+                data = json.load(f)
         self.root = root
         self.imgs = {im["id"]: im for im in data["images"]}
         self.anns_of = {}

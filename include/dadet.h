@@ -526,6 +526,32 @@ int dadet_rain_synthesize(const unsigned char* image_hwc, const unsigned char* m
                           const double* coeffs, const float* ws3, float c0, float c1, unsigned char* out_hwc,
                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* Instance boxes from Cityscapes instance-id maps (instance_boxes.hip), replacing the per-instance mask pass and contour trace
+ * of the reference's tools/cityscapes/convert_cityscapes_to_coco.py + instances2dict_with_polygons.py.
+ * ids: uint16 pixels of n maps packed back to back in device memory, 16-byte aligned, total_elements in all; map i is
+ * hw_host[2i] x hw_host[2i+1] (H, W; HOST array) and starts at element offsets_host[i] (HOST array; any offset, so a map
+ * of odd width puts its rows at odd 2-byte offsets).  Both tables are validated against total_elements before anything is
+ * launched and reach the kernel by value: the call never waits for the device.
+ * Every id 24000 .. 33999 present in a map yields one row  [id, x0, y0, x1, y1, pixelCount, fragmented]  (int32; the
+ * extent of ALL pixels carrying the id, inclusive), rows in ascending id: rows_out [n][SLOTS][COLUMNS] (the first
+ * counts_out[i] rows of map i are written, the rest is left as it was), counts_out int32 [n].  fragmented = 1 when one
+ * of the id's 8-connected components has at most 2 pixels (beyond the image there is no pixel).  Other ids are ignored.
+ * One clear of the workspace, one accumulation launch (a workgroup per TILE_H x TILE_W tile, runs found per SEGMENT of a
+ * row and merged in LDS before the table is touched) and one compaction launch, on `stream`.  Integer atomics only: the
+ * result is exact and independent of timing.  workspace: device memory, 4-byte aligned, sized by the query. */
+#define DADET_INSTANCE_BOXES_MAX_BATCH 32
+#define DADET_INSTANCE_BOXES_MAX_SIDE 32767
+#define DADET_INSTANCE_BOXES_FIRST_ID 24000
+#define DADET_INSTANCE_BOXES_SLOTS 10000
+#define DADET_INSTANCE_BOXES_COLUMNS 7
+#define DADET_INSTANCE_BOXES_TILE_W 256
+#define DADET_INSTANCE_BOXES_TILE_H 16
+#define DADET_INSTANCE_BOXES_SEGMENT 64
+int dadet_instance_boxes_workspace_bytes(int n, size_t* bytes_out);
+int dadet_instance_boxes(const unsigned short* ids, long long total_elements, const int* hw_host,
+                         const long long* offsets_host, int n, int* rows_out, int* counts_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Fused detection losses: value and gradient in one single-workgroup launch (losses.hip).
  * dadet_rpn_loss replaces RPNLossComputation.__call__'s loss part (modeling/rpn/loss.py:125-143): objectness /
  * box_regression are the flattened NHWC prediction maps ([N*H*W*A] and [N*H*W*A][4], the order of

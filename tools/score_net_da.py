@@ -24,6 +24,11 @@ domain-adaptation papers report, and writes `result.txt`.  `--dataset voc:DIR,SP
 no COCO form, so it is always scored VOC-style (`--metric coco` is then read as voc07, the reference's default), and with
 `--config-file` its evaluation pass runs in this process (one GPU) and leaves `predictions.pth` in
 `<output-dir>/inference/<DIR's name>_<SPLIT>/`: tools/test_net_da.py takes COCO-format sets only.
+`--dataset cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly]` names Cityscapes as unpacked from its archives (data/cityscapes.py,
+DESIGN.md 3h): a COCO-format set built from the id maps, scored with either metric.  With `--config-file` its annotations are
+written to `<output-dir>/<ROOT's name>_<SPLIT and options>.json` first and that file, with the split's image folder, is what
+tools/test_net_da.py (which takes annotation files) evaluates: `predictions.pth` lands in the folder of that name under
+`<output-dir>/inference/`.
 
 `--device-prep` (with `--config-file`): the evaluation pass runs in this process as well, for either kind of set, fed from the
 device input pipeline — test-time augmentation through `TEST.BBOX_AUG.ENABLED True` included."""
@@ -38,14 +43,24 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from da_detect_amd.data.build import dataset_from_spec  # noqa: E402
+from da_detect_amd.data.build import CITYSCAPES_PREFIX, dataset_from_spec, parse_dataset_spec  # noqa: E402
 from da_detect_amd.data.evaluation import evaluate  # noqa: E402
 from da_detect_amd.data.evaluation.voc import do_voc_evaluation  # noqa: E402
 
 
 def _pair(text):
+    if text.startswith(CITYSCAPES_PREFIX):       # cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly] (data/cityscapes.py)
+        return parse_dataset_spec(text)
     ann, root = text.split(",")
     return ann, root
+
+
+def _set_name(spec):
+    """the folder under <output-dir>/inference a set's predictions go to"""
+    for prefix in ("voc:", CITYSCAPES_PREFIX):
+        if spec[0].startswith(prefix):
+            return os.path.basename(spec[0][len(prefix):].rstrip("/")) + "_" + spec[1].replace(",", "_")
+    return os.path.splitext(os.path.basename(spec[0]))[0]
 
 
 def _evaluation_pass(args, folder):
@@ -78,7 +93,9 @@ def _evaluation_pass(args, folder):
 
 def main():
     ap = argparse.ArgumentParser(description="COCO box AP / proposal recall of saved predictions, on MI355X")
-    ap.add_argument("--dataset", type=_pair, required=True, help="annotation.json,image_root of the test set")
+    ap.add_argument("--dataset", type=_pair, required=True,
+                    help="annotation.json,image_root of the test set — or voc:DIR,SPLIT, or "
+                         "cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly]")
     ap.add_argument("--predictions", default=None, help="predictions.pth written by tools/test_net_da.py")
     ap.add_argument("--config-file", default=None, help="run tools/test_net_da.py with this yaml first, then score its output")
     ap.add_argument("--ckpt", default=None)
@@ -101,11 +118,16 @@ def main():
         if not args.output_dir:
             raise SystemExit("--config-file needs --output-dir: the evaluation pass leaves predictions.pth there")
         logging.basicConfig(level=logging.INFO)
-        voc = args.dataset[0].startswith("voc:")
-        name = os.path.basename(args.dataset[0][len("voc:"):].rstrip("/")) + "_" + args.dataset[1] if voc else \
-            os.path.splitext(os.path.basename(args.dataset[0]))[0]
-        folder = os.path.join(args.output_dir, "inference", name)
-        if voc or args.device_prep:
+        if args.dataset[0].startswith(CITYSCAPES_PREFIX):
+            # a COCO-format set: its annotations are written out once, as <output-dir>/<set name>.json, and from here on it is an
+            # (annotation file, image root) pair like any other — tools/test_net_da.py evaluates it, in its own process
+            from da_detect_amd.data.cityscapes import write_annotation_file
+
+            os.makedirs(args.output_dir, exist_ok=True)
+            args.dataset = write_annotation_file(args.dataset[0][len(CITYSCAPES_PREFIX):], args.dataset[1],
+                                                 os.path.join(args.output_dir, _set_name(args.dataset) + ".json"))
+        folder = os.path.join(args.output_dir, "inference", _set_name(args.dataset))
+        if args.dataset[0].startswith("voc:") or args.device_prep:
             _evaluation_pass(args, folder)
         else:
             run = [sys.executable, os.path.join(ROOT, "tools", "test_net_da.py"), "--config-file", args.config_file, "--dataset",

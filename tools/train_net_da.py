@@ -10,7 +10,7 @@ then engine.trainer.do_da_train.  One process per GPU:
 
 Differences to the reference script, on purpose: DistributedDataParallel is replaced by the bucketed gradient reducer
 attached to the fused optimizer (parallel/reducer.py); datasets are named by (annotation file, image root) pairs — or
-`voc:DIR,SPLIT` for PASCAL VOC layout — instead of the path catalog; there is no periodic evaluation (engine.inference.inference produces the bbox.json records)."""
+`voc:DIR,SPLIT` for PASCAL VOC layout, `cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly]` for raw Cityscapes — instead of the path catalog; there is no periodic evaluation (engine.inference.inference produces the bbox.json records)."""
 import argparse
 import logging
 import os
@@ -25,7 +25,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from da_detect_amd.config import cfg  # noqa: E402
-from da_detect_amd.data.build import make_da_data_loaders, make_triplet_data_loader  # noqa: E402
+from da_detect_amd.data.build import make_da_data_loaders, make_triplet_data_loader, parse_dataset_spec  # noqa: E402
 from da_detect_amd.engine.trainer import do_da_train, enable_overlapped_rpn_backward, train_step  # noqa: E402
 from da_detect_amd.modeling.detector import build_detection_model  # noqa: E402
 from da_detect_amd.parallel.reducer import BucketedGradReducer  # noqa: E402
@@ -45,17 +45,17 @@ def setup_seed(seed):
 
 
 def _pair(text):
-    if text.startswith("rain:"):        # --auxiliary rain:MASKDIR: the source images under synthesised rain (data/rain.py)
-        return text, ""
-    ann, root = text.split(",")
-    return ann, root
+    """ann.json,imgdir | voc:DIR,SPLIT | rain:MASKDIR (the source images under synthesised rain, data/rain.py) |
+    cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly] (raw Cityscapes, data/cityscapes.py)"""
+    return parse_dataset_spec(text)
 
 
 def main():
     ap = argparse.ArgumentParser(description="DA Faster R-CNN training on MI355X")
     ap.add_argument("--config-file", required=True)
-    ap.add_argument("--source", type=_pair, help="ann.json,imgdir — or voc:DIR,SPLIT for a dataset in PASCAL VOC layout "
-                                                 "(likewise --target and --auxiliary)")
+    ap.add_argument("--source", type=_pair, help="ann.json,imgdir — or voc:DIR,SPLIT for a dataset in PASCAL VOC layout, or "
+                                                 "cityscapes:ROOT,SPLIT[,foggy[=BETA]|rain][,caronly] for Cityscapes as unpacked "
+                                                 "from its archives (likewise --target and --auxiliary)")
     ap.add_argument("--target", type=_pair)
     ap.add_argument("--auxiliary", type=_pair,
                     help="ann.json,imgdir of the rainy renderings — or rain:MASKDIR to synthesise them per sample from the "

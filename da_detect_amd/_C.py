@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import amax as _amax
+from . import weights as _weights
 from ._lib import ConvDesc
 
 CL = torch.channels_last
@@ -155,7 +156,7 @@ def _weight_amax(w):
         w = like()
     base = w._base if w._base is not None else w
     if isinstance(base, torch.nn.Parameter) or w.__dict__.get("_dadet_persistent"):
-        return _amax.WEIGHTS.ptr(w, _TRANSPOSES.epoch)
+        return _amax.WEIGHTS.ptr(w, _weights.epoch())
     return _amax.ptr(w)
 
 
@@ -552,143 +553,8 @@ def _conv_forward_call(d, x, w, scale, bias, addend, mask_ref, out, ax, aw):
     _amax.attach(out, slot)
 
 
-def _transpose_now(w, scale, wt):
-    Cout, Cin, KH, KW = w.shape
-    cout_pad = wt.shape[1]          # rows of the result: >= Cout (zero columns behind the weight's own)
-    _lib.call("dadet_conv_weight_transpose_padded", _p(w), _p(scale), _p(wt), Cout, KH, KW, Cin, cout_pad, _stream())
-    return wt
-
-
-class _TransposeCache(object):
-    """Transposed (tap-flipped, FrozenBN-folded) weights for the data-gradient GEMMs, refreshed for ALL registered weights
-    by ONE launch per optimizer step instead of one launch in front of every data-gradient GEMM.
-
-    An entry (weight storage, shape, scale storage) owns a persistent output buffer.  It is valid while (a) the weight's
-    autograd version is the one it was computed from and (b) the weight epoch is — the epoch is what in-place updates
-    through raw pointers bump (FusedSGD.step -> bump_weight_epoch(); ATen's in-place ops bump the version themselves).
-    The first request of an epoch recomputes every entry in one batched launch on the current stream; a weight seen for
-    the first time is transposed on the spot and joins the table.  `enabled = False`: one launch per request."""
-
-    def __init__(self):
-        self.entries = {}
-        self.epoch = 0
-        self.batched_epoch = -1
-        self.table = None          # (device tensor, n, total_blocks, keys)
-        self.ready = None          # (stream, event) of the last batched refresh
-        self.enabled = True
-        self._from_bump = False
-        self._trained_only = False
-
-    def bump(self, device=None, trained_only=False):
-        """new weight epoch; with a device: refresh every entry at once, on the caller's stream (the optimizer's, behind
-        the update and behind everything that read the old buffers).  trained_only: the caller changed trainable parameters
-        only (the optimizer): frozen weights' maxima are left alone (amax.WeightSlots.refresh)"""
-        self.epoch += 1
-        self._trained_only = bool(trained_only)
-        if self.enabled and device is not None and self.entries:
-            self._from_bump = True
-            try:
-                self._refresh_all(device)
-            finally:
-                self._from_bump = False
-        elif device is not None and _mode4():
-            # no transposed copies registered: the weights' maxima alone
-            _amax.WEIGHTS.refresh(device, self.epoch, trained_only=self._trained_only)
-        self._trained_only = False
-
-    def _single(self, e, w, scale):
-        """one entry on the current stream, remembered with an event for readers on other streams"""
-        _transpose_now(w, scale, e["wt"])
-        _amax.WEIGHTS.invalidate(e["wt"])
-        e["epoch"] = self.epoch
-        if w.is_cuda:
-            st = torch.cuda.current_stream(w.device)
-            e["ev"] = (st, st.record_event())
-        return e["wt"]
-
-    def get(self, w, scale, cout_pad=0):
-        Cout, Cin, KH, KW = w.shape
-        key = (w.data_ptr(), Cout, Cin, KH, KW, scale.data_ptr() if scale is not None else 0, w.device.index, cout_pad)
-        e = self.entries.get(key)
-        if e is None:
-            wt = torch.empty((Cin, max(Cout, cout_pad), KH, KW), dtype=torch.float32, device=w.device, memory_format=CL)
-            # the entry keeps w / scale alive: their storage addresses are in the device table
-            wt._dadet_persistent = True    # its largest magnitude lives in amax.WEIGHTS (mode 4)
-            e = self.entries[key] = dict(w=w, scale=scale, wt=wt, version=w._version, epoch=self.epoch, used=self.epoch,
-                                         ev=None)
-            self.table = None
-            return self._single(e, w, scale)
-        e["used"] = self.epoch
-        if e["version"] != w._version:
-            e["w"], e["version"] = w, w._version
-            return self._single(e, w, scale)
-        if e["epoch"] != self.epoch:
-            if self.batched_epoch != self.epoch:
-                self._refresh_all(w.device)
-            if e["epoch"] != self.epoch:      # joined the table after this epoch's launch
-                return self._single(e, w, scale)
-        # produced on ONE stream (the optimizer's for the batched refresh): a reader on another stream waits for it
-        src = e["ev"] if e["ev"] is not None else self.ready
-        if src is not None and w.is_cuda and torch.cuda.current_stream(w.device) != src[0]:
-            torch.cuda.current_stream(w.device).wait_event(src[1])
-        return e["wt"]
-
-    def _refresh_all(self, device):
-        # weights nobody asked for during the last two epochs belong to a model that is gone: dropped (with their buffers)
-        for k in [k for k, e in self.entries.items() if e["used"] < self.epoch - 2]:
-            del self.entries[k]
-        live = [(k, e) for k, e in self.entries.items() if k[6] == device.index and e["version"] == e["w"]._version]
-        if not live:
-            self.batched_epoch = self.epoch
-            return
-        if self.table is None or self.table[3] != [k for k, _ in live]:
-            arr = (_lib.TransposeItem * len(live))()
-            blocks = 0
-            for i, (k, e) in enumerate(live):
-                _, Cout, Cin, KH, KW, _, _, cout_pad = k
-                it = arr[i]
-                it.w, it.scale, it.wt = e["w"].data_ptr(), (e["scale"].data_ptr() if e["scale"] is not None else None), \
-                    e["wt"].data_ptr()
-                it.Cout, it.KH, it.KW, it.Cin = Cout, KH, KW, Cin
-                it.cout_pad = cout_pad
-                it.blocks_ci, it.blocks_co = (Cin + 31) // 32, (max(Cout, cout_pad) + 31) // 32
-                it.first_block = blocks
-                blocks += it.blocks_ci * it.blocks_co * KH * KW
-            host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-            self.table = (host.to(device), len(live), blocks, [k for k, _ in live])
-        dev_t, n, blocks, _ = self.table
-        _lib.call("dadet_conv_weight_transpose_batch", _p(dev_t), n, blocks, _stream())
-        for _, e in live:
-            e["epoch"] = self.epoch
-            e["ev"] = None
-        self.batched_epoch = self.epoch
-        if _mode4():
-            # parameters and the transposed copies just written: every persistent operand's maximum in one launch.  Behind
-            # the optimizer (bump with a device) no other stream reads the slots; from the middle of a step they may.
-            _amax.WEIGHTS.refresh(device, self.epoch, sync=not self._from_bump,
-                                  trained_only=self._from_bump and self._trained_only)
-        if device.type == "cuda":
-            st = torch.cuda.current_stream(device)
-            self.ready = (st, st.record_event())
-
-
-_TRANSPOSES = _TransposeCache()
-
-
-def weight_epoch():
-    """counts the in-place weight updates made through raw pointers (see bump_weight_epoch)"""
-    return _TRANSPOSES.epoch
-
-
-def bump_weight_epoch(device=None, trained_only=False):
-    """weights were updated in place through raw pointers (the fused SGD kernel) or through `.data` (a broadcast, a
-    checkpoint load, an EMA, a manual `p.data.copy_`): cached derived forms are stale.  REQUIRED after any weight write
-    that does not go through autograd's version counter — the data-gradient GEMMs otherwise keep using the transposed /
-    padded copies of the old values, and (contraction mode 4) the old largest magnitude of the weight: a weight that grew
-    past twice its recorded maximum overflows fp16's range inside the GEMM and the step ends in inf / nan, loudly.
-    FusedSGD.step, BucketedGradReducer.broadcast_parameters and Checkpointer.load call it themselves.
-    trained_only=True (the optimizer): only tensors with requires_grad changed — frozen weights keep their maxima."""
-    _TRANSPOSES.bump(device, trained_only)
+# weights written without autograd's version counter seeing it (the fused SGD kernel, `.data`): weights.bump says who must call
+weight_epoch, bump_weight_epoch = _weights.epoch, _weights.bump
 
 
 def conv_weight_transpose(w, scale=None, cout_pad=0):
@@ -703,10 +569,10 @@ def conv_weight_transpose(w, scale=None, cout_pad=0):
     # cached only for storage that persists across steps — a trainable parameter or a view of one (a temporary's address may
     # be handed to another tensor by the allocator, and the cache is keyed by address)
     base = w._base if w._base is not None else w
-    if _TRANSPOSES.enabled and base.is_leaf and base.requires_grad:
-        return _TRANSPOSES.get(w, scale, cout_pad)
+    if base.is_leaf and base.requires_grad:
+        return _weights.TRANSPOSES.get(w, scale, cout_pad)
     wt = torch.empty((Cin, max(Cout, cout_pad), KH, KW), dtype=torch.float32, device=w.device, memory_format=CL)
-    return _transpose_now(w, scale, wt)
+    return _weights.transpose_now(w, scale, wt)
 
 
 class WgradBatch(list):

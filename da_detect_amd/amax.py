@@ -21,11 +21,11 @@ here ever brings a maximum to the host.  Where slots come from:
 `MEASURED` counts the one-pass measurements (tools / tests read it to see which producers still lack a fused maximum).
 """
 import ctypes
-import weakref
 
 import torch
 
 from . import _lib
+from .weights import Stamp
 
 STRIDE = 1 << 16     # DADET_AMAX_STRIDE
 _POOL_SLOTS = STRIDE
@@ -117,8 +117,8 @@ def ptr(t):
 
 class WeightSlots(object):
     """Slots of tensors that persist across steps and change once per step: parameters (updated in place by the fused
-    optimizer through raw pointers — no version bump, hence the explicit epoch) and the transposed-weight buffers of the
-    data-gradient GEMMs.  Keyed by (address, numel).  An entry holds a WEAK reference to the tensor that owns the storage
+    optimizer through raw pointers — no version bump, hence the weight epoch) and the transposed-weight buffers of the
+    data-gradient GEMMs.  Keyed by (address, numel).  An entry carries a weights.Stamp of the tensor that owns the storage
     (the parameter itself for a view of one): when a model is gone its entries are swept and their slots reused."""
 
     CAP = 4096
@@ -137,25 +137,18 @@ class WeightSlots(object):
         return d
 
     @staticmethod
-    def _covers(o, e):
-        """does tensor o still own the recorded address range?  (`p.data = ...`, model.to() / .float() and re-flattening
-        replace a parameter's storage while the Python object — and its version counter — live on)"""
-        try:
-            st = o.untyped_storage()
-            base = st.data_ptr()
-            return base <= e["ptr"] and e["ptr"] + 4 * e["n"] <= base + st.nbytes()
-        except RuntimeError:
-            return False
+    def _stamp(owner, epoch):
+        # a buffer that is no parameter (a transposed copy) is rewritten behind every optimizer step
+        return Stamp.of(owner, epoch=epoch, trained=None if isinstance(owner, torch.nn.Parameter) else True)
 
     @staticmethod
     def _alive(e):
-        o = e["ref"]()
-        return o is not None and o._version == e["version"] and WeightSlots._covers(o, e)
+        """the owner still exists, unwritten through ATen, on the storage the entry's address lies in"""
+        return e["stamp"].intact()
 
     def _sweep(self, d, epoch):
-        """forget entries whose owner is gone, or that nobody asked about during the last two epochs"""
-        dead = [k for k, e in d["entries"].items()
-                if e["ref"]() is None or e["used"] < epoch - 2 or not self._covers(e["ref"](), e)]
+        """forget entries whose owner is gone, written or moved, or that nobody asked about during the last two epochs"""
+        dead = [k for k, e in d["entries"].items() if e["used"] < epoch - 2 or not self._alive(e)]
         for k in dead:
             d["free"].append(d["entries"].pop(k)["i"])
         if dead:
@@ -172,26 +165,23 @@ class WeightSlots(object):
         key = (t.data_ptr(), t.numel())
         e = d["entries"].get(key)
         owner = t._base if t._base is not None else t
-        if e is not None and e["ref"]() is not owner:        # the address went to another tensor
-            d["free"].append(d["entries"].pop(key)["i"])
-            d["table"] = d["table_trained"] = None
-            e = None
         if e is None:
             if not d["free"]:
                 self._sweep(d, epoch)
             if not d["free"]:
                 raise _lib.DadetError("amax: more than %d persistent GEMM operands alive" % self.CAP)
-            e = d["entries"][key] = dict(ref=weakref.ref(owner), ptr=key[0], n=key[1], i=d["free"].pop(),
-                                         version=owner._version, epoch=epoch, used=epoch)
+            e = d["entries"][key] = dict(stamp=self._stamp(owner, epoch), ptr=key[0], n=key[1], i=d["free"].pop(),
+                                         used=epoch)
             d["table"] = d["table_trained"] = None
             self._measure_one(d, e)
         else:
             e["used"] = epoch
-            if e["version"] != owner._version or e["epoch"] != epoch:
-                if e["version"] == owner._version and d["epoch"] != epoch:
-                    self.refresh(t.device, epoch, sync=True)
-                if e["version"] != owner._version or e["epoch"] != epoch:
-                    e["version"], e["epoch"] = owner._version, epoch
+            if not e["stamp"].holds(owner, epoch=epoch):
+                if d["epoch"] != epoch and e["stamp"].intact(owner):
+                    self.refresh(t.device, epoch, sync=True)       # the first request of an epoch: everything at once
+                if not e["stamp"].holds(owner, epoch=epoch):
+                    # written through ATen, the address went to another tensor, or it joined after this epoch's launch
+                    e["stamp"] = self._stamp(owner, epoch)
                     self._measure_one(d, e)
         return ctypes.c_void_p(d["slots"].data_ptr() + 4 * e["i"])
 
@@ -200,31 +190,22 @@ class WeightSlots(object):
         d = self._dev(t.device)
         e = d["entries"].get((t.data_ptr(), t.numel()))
         if e is not None:
-            e["epoch"] = -1
-
-    @staticmethod
-    def _frozen(e):
-        """the entry's storage belongs to a parameter no optimizer changes (a frozen stage's weight)"""
-        o = e["ref"]()
-        return isinstance(o, torch.nn.Parameter) and not o.requires_grad
+            e["stamp"].void()
 
     def refresh(self, device, epoch, sync=False, trained_only=False):
         """every registered tensor of this device re-measured by one fill + one launch on the current stream.  sync: the
         call comes from the middle of a step (not from behind the optimizer): other streams may still read the slots.
-        trained_only (the optimizer's call): frozen parameters keep their slots UNTOUCHED — their values did not change, and
-        the next step's frozen prefix may be reading them on the compute stream while this runs on the optimizer lane
-        (utils.streams: a slot is zero between the fill and the launch that re-measures it)."""
+        trained_only (the optimizer's call): entries whose stamp still holds — frozen parameters without a full bump since —
+        keep their slots UNTOUCHED: the next step's frozen prefix may be reading them on the compute stream while this runs
+        on the optimizer lane (utils.streams: a slot is zero between the fill and the launch that re-measures it)."""
         if sync:
             torch.cuda.synchronize(device)
         d = self._dev(device)
         d["epoch"] = epoch
         self._sweep(d, epoch)
-        live = [e for e in d["entries"].values() if self._alive(e)]
+        live = list(d["entries"].values())
         if trained_only:
-            for e in live:
-                if self._frozen(e):
-                    e["epoch"] = epoch
-            live = [e for e in live if not self._frozen(e)]
+            live = [e for e in live if not e["stamp"].holds(epoch=epoch)]
         if not live:
             return
         keys = [(e["i"], e["ptr"], e["n"]) for e in live]
@@ -252,7 +233,7 @@ class WeightSlots(object):
             d["slots"].index_fill_(1, idx, 0.0)
         _lib.call("dadet_amax_batch", ctypes.c_void_p(dev_t.data_ptr()), n, blocks, _stream())
         for e in live:
-            e["epoch"] = epoch
+            e["stamp"].renew(epoch)
 
 
 WEIGHTS = WeightSlots()

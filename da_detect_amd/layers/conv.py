@@ -6,7 +6,6 @@ calls per layer (reference: maskrcnn_benchmark/modeling/backbone/resnet.py:294-3
 Backward = ReLU/affine gating kernel, data gradient by the same forward kernel on transposed weights,
 weight gradient by the split-K wgrad kernel, bias gradient by a column sum.
 """
-import weakref
 
 import torch
 import torch.nn.functional as F
@@ -16,6 +15,7 @@ from torch.autograd.function import once_differentiable
 from .. import _C
 from .. import amax as _amax
 from ..utils.streams import WgradLane, bias_grad
+from ..weights import Stamp
 
 CL = torch.channels_last
 
@@ -106,7 +106,7 @@ def linear(x, weight, bias=None, relu=False):
     return y[:, :out_f] if pad else y
 
 
-_FUSED_1X1 = {}      # (ids of the weights and biases) -> (stamp, fused weight, fused bias, weak references): conv1x1_multi
+_FUSED_1X1 = {}      # (ids of the weights and biases) -> (weights.Stamp of them, fused weight, fused bias): conv1x1_multi
 
 
 def conv1x1_multi(x, weights, biases, relu=False):
@@ -116,27 +116,25 @@ def conv1x1_multi(x, weights, biases, relu=False):
     sizes = [w.shape[0] for w in weights]
     total = sum(sizes)
     pad = (-total) % 4
-    key = stamp = None
-    if not torch.is_grad_enabled() and all(t.is_cuda for t in weights):
-        # no graph to build (the shared RPN head of a pyramid runs five times per step like this): the fused weight / bias
-        # of one weight epoch are built once — 4 launches per call otherwise, and one more pass for the fused weight's
-        # largest magnitude (contraction mode 4)
-        key = tuple(id(t) for t in list(weights) + list(biases))
-        stamp = (_C.weight_epoch(),) + tuple(t._version for t in list(weights) + list(biases))
-        hit = _FUSED_1X1.get(key)
-        if hit is not None and hit[0] == stamp and all(r() is t for r, t in zip(hit[3], list(weights) + list(biases))):
-            w, b = hit[1], hit[2]
-            key = None
-    if key is not None or stamp is None:
+    # no graph to build (the shared RPN head of a pyramid runs five times per step like this): the fused weight / bias are
+    # built once per change of their sources — 4 launches per call otherwise, and one more pass for the fused weight's
+    # largest magnitude (contraction mode 4)
+    cached = not torch.is_grad_enabled() and all(t.is_cuda for t in weights)
+    sources = list(weights) + list(biases)
+    key = tuple(id(t) for t in sources) if cached else None
+    hit = _FUSED_1X1.get(key) if cached else None
+    if hit is not None and hit[0].holds(*sources):
+        w, b = hit[1], hit[2]
+    else:
         w = torch.cat([wi.reshape(wi.shape[0], wi.shape[1], 1, 1) for wi in weights], 0)
         b = torch.cat(list(biases), 0)
         if pad:
             w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, pad))
             b = F.pad(b, (0, pad))
-        if key is not None:
+        if cached:
             if len(_FUSED_1X1) > 64:
                 _FUSED_1X1.clear()
-            _FUSED_1X1[key] = (stamp, w, b, [weakref.ref(t) for t in list(weights) + list(biases)])
+            _FUSED_1X1[key] = (Stamp.of(*sources), w, b)
     y = conv2d_affine_act(x, w, None, b, relu=relu)
     outs, o = [], 0
     for s in sizes:

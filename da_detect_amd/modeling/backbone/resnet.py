@@ -7,6 +7,7 @@ What differs is the execution: every conv -> FrozenBN -> (+identity) -> ReLU gro
 (the affine, the residual add and the ReLU live in the GEMM epilogue), activations stay NHWC end to end, and
 the 3-channel stem input is staged as NHWC4 so the 7x7 conv is an implicit GEMM over a 7x8x4 window.
 """
+import weakref
 from collections import namedtuple
 
 import torch
@@ -18,6 +19,7 @@ from ...layers import Conv2d, FrozenBatchNorm2d, conv2d_affine_act
 from ...utils.registry import Registry
 from ...utils import streams
 from ...utils.streams import WgradLane
+from ...weights import Stamp
 
 StageSpec = namedtuple("StageSpec", ["index", "block_count", "return_features"])
 
@@ -264,53 +266,40 @@ class _PaddedWeights(object):
     contract over them), kept in persistent buffers.  Padding on the spot cost 5 launches per deformable block and forward
     pass (two F.pad = fill + copy each, one layout copy): 150 launches of ~6 us per step of R-101-FPN-DCN.  Here every
     registered parameter is refreshed by ONE multi-tensor copy, the first time one of them is asked for after the weights
-    changed (autograd version of the parameter, or the weight epoch that the fused optimizer bumps)."""
+    changed (weights.Stamp)."""
 
     def __init__(self):
-        self.entries = {}          # id(weight) -> dict(ref, wp, bp, bias_ref)
-        self.stamp = None
+        self.entries = {}          # id(weight) -> dict(stamp of (weight, bias), wp, bp)
 
-    def _stamp(self):
-        ws = [e["w"]() for e in self.entries.values()]
-        bs = [e["b"]() for e in self.entries.values() if e["b"] is not None]
-        if any(t is None for t in ws) or any(t is None for t in bs):
-            return None                                    # a parameter is gone: rebuild
-        return (_C.weight_epoch(), tuple(t._version for t in ws), tuple(t._version for t in bs))
-
-    def _fresh(self):
-        stamp = self._stamp()
-        if stamp is not None and stamp == self.stamp:
-            return
-        for k in [k for k, e in self.entries.items() if e["w"]() is None or (e["b"] is not None and e["b"]() is None)]:
-            del self.entries[k]
+    def _refresh(self):
         dst, src = [], []
-        for e in self.entries.values():
-            w = e["w"]()
+        for k, e in list(self.entries.items()):
+            w, b = e["stamp"].sources()
+            if w is None or (b is None) != (e["bp"] is None):      # a parameter is gone
+                del self.entries[k]
+                continue
             dst.append(e["wp"][:w.shape[0]])
             src.append(w.detach())
-            if e["b"] is not None:
+            if b is not None:
                 dst.append(e["bp"][:w.shape[0]])
-                src.append(e["b"]().detach())
+                src.append(b.detach())
+            e["stamp"] = Stamp.of(w, b)
         if dst:
             torch._foreach_copy_(dst, src)
-        self.stamp = self._stamp()
 
     def get(self, weight, bias, pad):
-        import weakref
-
         e = self.entries.get(id(weight))
-        if e is None or e["w"]() is not weight or (bias is not None) != (e["b"] is not None) \
-                or (bias is not None and e["b"]() is not bias):
+        was = e["stamp"].sources() if e is not None else None
+        if e is None or was[0] is not weight or was[1] is not bias:
             cout, cin, kh, kw = weight.shape
             wp = torch.zeros((cout + pad, cin, kh, kw), dtype=weight.dtype, device=weight.device).contiguous(
                 memory_format=torch.channels_last)
             bp = torch.zeros(cout + pad, dtype=bias.dtype, device=bias.device) if bias is not None else None
             wp._dadet_amax_like = weakref.ref(weight)     # same largest magnitude as the parameter (amax.py, mode 4)
-            self.entries[id(weight)] = dict(w=weakref.ref(weight), b=weakref.ref(bias) if bias is not None else None,
-                                            wp=wp, bp=bp)
-            self.stamp = None
-        self._fresh()
-        e = self.entries[id(weight)]
+            e = self.entries[id(weight)] = dict(stamp=Stamp.of(weight, bias), wp=wp, bp=bp)
+            e["stamp"].void()
+        if not e["stamp"].holds(weight, bias):      # after a bump every entry is stale: all of them by this one copy
+            self._refresh()
         return e["wp"], e["bp"]
 
 
@@ -488,11 +477,9 @@ class BaseStem(nn.Module):
         w = self.conv1.weight
         if w.requires_grad and torch.is_grad_enabled():
             return F.pad(w, (0, 1, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last)
-        # (the weight epoch: the fused optimizer updates a trainable stem through raw pointers, without a version bump)
-        key = (w._version, w.device, _C.weight_epoch() if w.requires_grad else 0)
-        if self._w4 is None or self._w4[0] != key:
+        if self._w4 is None or not self._w4[0].holds(w):
             with torch.no_grad():
-                self._w4 = (key, F.pad(w, (0, 1, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last))
+                self._w4 = (Stamp.of(w), F.pad(w, (0, 1, 0, 0, 0, 1)).contiguous(memory_format=torch.channels_last))
         return self._w4[1]
 
     def forward(self, x):

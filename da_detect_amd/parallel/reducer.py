@@ -301,7 +301,7 @@ class BucketedGradReducer(object):
             for p in self.params:
                 dist.broadcast(p.data, src=src, group=self.group)
             # a write through .data does not bump the tensors' autograd version: the caches of transposed / padded weights
-            # (_C._TransposeCache, backbone.resnet._PaddedWeights) are keyed by (version, weight epoch)
+            # (weights.Stamp) see it through the weight epoch only
             from .. import _C
             _C.bump_weight_epoch()
 

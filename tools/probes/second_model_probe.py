@@ -16,7 +16,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from da_detect_amd import _C  # noqa: E402
+from da_detect_amd import weights  # noqa: E402
 from da_detect_amd.data.synthetic import make_batch  # noqa: E402
 from da_detect_amd.engine.trainer import enable_overlapped_rpn_backward, train_step  # noqa: E402
 from da_detect_amd.utils import streams  # noqa: E402
@@ -49,7 +49,7 @@ def run(name, steps, profile=False):
         torch.cuda.synchronize()
         pr.disable()
         pstats.Stats(pr).sort_stats("tottime").print_stats(25)
-    tc = _C._TRANSPOSES
+    tc = weights.TRANSPOSES
     print("tables: transposed-weight cache %d entries; pending reductions %d; side streams %d; hooks on params %d" % (
         len(getattr(tc, "entries", {}) or {}), len(streams._PENDING_REDUCES), len(streams._SIDE),
         sum(len(getattr(p, "_post_accumulate_grad_hooks", None) or {}) for p in model.parameters())))

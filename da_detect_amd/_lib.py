@@ -78,6 +78,16 @@ class ImageItem(ctypes.Structure):
 
 
 IMAGE_BATCH_MAX = 8      # DADET_IMAGE_BATCH_MAX
+FLIP_H, FLIP_V = 1, 2    # DADET_FLIP_H / DADET_FLIP_V: the bits of an image item's flip mask
+JITTER_BATCH_MAX = 8     # DADET_JITTER_BATCH_MAX
+JITTER_MAX_OPS = 4       # DADET_JITTER_MAX_OPS
+
+
+class JitterItem(ctypes.Structure):
+    """mirror of dadet_jitter_item (include/dadet.h)"""
+
+    _fields_ = [("src", c_void_p), ("out", c_void_p)] + [(n, c_int) for n in ("H", "W", "n_ops", "hue_shift")] + [
+        ("op", c_int * JITTER_MAX_OPS), ("factor", c_float * JITTER_MAX_OPS)]
 
 
 # name -> argtypes ; every function returns int (status) unless listed in _RESTYPES
@@ -154,6 +164,7 @@ _SIGNATURES = {
                                          POINTER(c_float), _P, c_int, _P],
     "dadet_image_prepare_batch": [POINTER(ImageItem), c_int, c_int, POINTER(c_float), POINTER(c_float), _P, c_int, c_int,
                                   c_int, _P],
+    "dadet_color_jitter_batch": [POINTER(JitterItem), c_int, _P, _P],
     "dadet_rain_scratch_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
     "dadet_rain_synthesize": [_P, _P, c_int, c_int, c_int, POINTER(ctypes.c_double), POINTER(c_float), c_float, c_float, _P, _P,
                               c_size_t, _P],

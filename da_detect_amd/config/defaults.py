@@ -74,6 +74,9 @@ _DEFAULTS = {
     "INPUT": {
         "MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
         "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True,
+        # training-time ColorJitter (0: that operator is off) and flip probabilities (config/defaults.py:58-65)
+        "BRIGHTNESS": 0.0, "CONTRAST": 0.0, "SATURATION": 0.0, "HUE": 0.0,
+        "HORIZONTAL_FLIP_PROB_TRAIN": 0.5, "VERTICAL_FLIP_PROB_TRAIN": 0.0,
     },
     "DATASETS": {"TRAIN": (), "SOURCE_TRAIN": (), "TARGET_TRAIN": (), "TARGET_TRAIN_negative": (), "TEST": (),
                  "TEST_SOURCE": ()},

@@ -1,4 +1,4 @@
-// Input pipeline on the device: Pillow-exact bilinear resize of a decoded RGB image, horizontal flip, BGR-255
+// Input pipeline on the device: Pillow-exact bilinear resize of a decoded RGB image, horizontal / vertical flip, BGR-255
 // conversion and mean / std normalisation, written straight into the padded batch tensor (gfx950).
 //
 // What it replaces (all host-side in the reference, per image and per worker process):
@@ -83,8 +83,9 @@ __global__ void resample_v_normalize_kernel(const unsigned char* __restrict__ in
     c1 = c1 * 255.f;
     c2 = t * 255.f;
   }
-  const int xo = flip ? (w - 1 - x) : x;
-  float* o = out + ((size_t)yy * row_stride + xo) * 3;
+  const int xo = (flip & DADET_FLIP_H) ? (w - 1 - x) : x;
+  const int yo = (flip & DADET_FLIP_V) ? (out_h - 1 - yy) : yy;
+  float* o = out + ((size_t)yo * row_stride + xo) * 3;
   o[0] = (c0 - m0) / s0;
   o[1] = (c1 - m1) / s1;
   o[2] = (c2 - m2) / s2;
@@ -93,8 +94,8 @@ __global__ void resample_v_normalize_kernel(const unsigned char* __restrict__ in
 // ---------------------------------------------------------------------------------------------- one launch per batch
 // Both passes, the conversion and the zero padding of up to kPrepMaxImages images in one launch.  Grid = (tiles in x,
 // tiles in y, image) over the PADDED canvas [Hp][Wp]; a workgroup owns one kPrepTileH x kPrepTileW tile of it and writes
-// every pixel of that tile once: image pixels inside [out_h, out_w] (mirrored columns stay inside [0, out_w)), zeros
-// beyond.  Inside the image the workgroup runs the horizontal pass for the input rows its output rows draw from into
+// every pixel of that tile once: image pixels inside [out_h, out_w] (mirrored columns stay inside [0, out_w), mirrored
+// rows inside [0, out_h): the workgroups then write each other's image pixels, every pixel still once), zeros beyond.  Inside the image the workgroup runs the horizontal pass for the input rows its output rows draw from into
 // LDS (8-bit, rounded with clip8 like resample_h_kernel: Pillow rounds between the passes), then the vertical pass
 // from LDS in registers.  The input rows are walked in chunks of kPrepChunkRows: a tile of 16 output rows draws from
 // 15 * f + 2 * ceil(f) + 1 input rows at a vertical factor f = H / out_h, so one chunk holds the tile up to f = 3 (the
@@ -224,8 +225,10 @@ __global__ __launch_bounds__(kPrepThreads) void prepare_batch_kernel(PrepBatch b
       c2 = t * 255.f;
     }
     const int x = x0 + px;
-    const int xo = d.flip ? (d.out_w - 1 - x) : x;
-    float* o = slot + ((size_t)(y0 + py) * Wp + xo) * 3;
+    const int y = y0 + py;
+    const int xo = (d.flip & DADET_FLIP_H) ? (d.out_w - 1 - x) : x;
+    const int yo = (d.flip & DADET_FLIP_V) ? (d.out_h - 1 - y) : y;       // mirrored rows stay inside [0, out_h)
+    float* o = slot + ((size_t)yo * Wp + xo) * 3;
     o[0] = (c0 - m0) / s0;
     o[1] = (c1 - m1) / s1;
     o[2] = (c2 - m2) / s2;
@@ -253,8 +256,9 @@ extern "C" int dadet_image_resample_v_normalize(const unsigned char* image_hwc, 
   DADET_REQUIRE(image_hwc && mean3 && std3 && out_hw3, "image_resample_v_normalize: null pointer");
   DADET_REQUIRE(bounds || out_h == in_h, "image_resample_v_normalize: no coefficient table but out_h != in_h");
   DADET_REQUIRE(!bounds || (coeffs && ksize > 0), "image_resample_v_normalize: missing coefficients");
+  DADET_REQUIRE(flip >= 0 && flip <= (DADET_FLIP_H | DADET_FLIP_V), "image_resample_v_normalize: flip mask %d (0 .. 3)", flip);
   hipLaunchKernelGGL(resample_v_normalize_kernel, dim3(ceil_div(w, 256), out_h), dim3(256), 0, as_stream(stream),
-                     image_hwc, in_h, w, bounds, coeffs, ksize, out_h, flip ? 1 : 0, to_bgr255 ? 1 : 0, mean3[0],
+                     image_hwc, in_h, w, bounds, coeffs, ksize, out_h, flip, to_bgr255 ? 1 : 0, mean3[0],
                      mean3[1], mean3[2], std3[0], std3[1], std3[2], out_hw3, out_row_stride);
   return check_launch("image_resample_v_normalize");
 }
@@ -271,6 +275,8 @@ extern "C" int dadet_image_prepare_batch(const dadet_image_item* items, int n, i
     DADET_REQUIRE(d.src && d.H > 0 && d.W > 0 && d.out_h > 0 && d.out_w > 0, "image_prepare_batch: image %d: bad dims", i);
     DADET_REQUIRE(d.out_h <= Hp && d.out_w <= Wp, "image_prepare_batch: image %d: %d x %d does not fit the %d x %d canvas",
                   i, d.out_h, d.out_w, Hp, Wp);
+    DADET_REQUIRE(d.flip >= 0 && d.flip <= (DADET_FLIP_H | DADET_FLIP_V), "image_prepare_batch: image %d: flip mask %d (0 .. 3)", i,
+                  d.flip);
     DADET_REQUIRE(d.slot >= 0 && d.slot < n_slots, "image_prepare_batch: image %d: slot %d of %d", i, d.slot, n_slots);
     DADET_REQUIRE(d.h_bounds ? (d.h_coeffs && d.h_ksize > 0) : d.out_w == d.W,
                   "image_prepare_batch: image %d: horizontal table missing or incomplete", i);

@@ -16,7 +16,8 @@ from ..structures.bounding_box import BoxList
 MIN_KEYPOINTS_PER_IMAGE = 10
 
 # what a `decode_to_tensor=True` dataset with transforms puts into a sample's image slot: the decoded pixels (uint8 [H,W,3],
-# CPU) and the decisions its transforms WOULD apply, decision = ((out_h, out_w), flip) — data/device_prep.py applies them
+# CPU) and the decisions its transforms WOULD apply, decision = ((out_h, out_w), flip) — with a vertical flip or a colour jitter
+# in the chain ((out_h, out_w), flip, vertical flip, jitter operators), data/transforms.py draw_decisions — data/device_prep.py applies them
 RawImage = collections.namedtuple("RawImage", ["pixels", "decision"])
 
 

@@ -1,11 +1,12 @@
 """Batch preparation on the GPU: decoded uint8 RGB images in, the model's padded fp32 batch out.
 
 One kernel launch per batch (csrc/image.hip, dadet_image_prepare_batch) replaces the reference's per-sample host chain Resize ->
-RandomHorizontalFlip -> ToTensor -> Normalize (data/transforms/transforms.py:32-97) and the collator's zero padding
-(data/collate_batch.py:46-55, structures/image_list.py:49-91).  The resize is Pillow's bilinear resample reproduced bit
+RandomHorizontalFlip -> RandomVerticalFlip -> ToTensor -> Normalize (data/transforms/transforms.py:32-97) and the collator's
+zero padding (data/collate_batch.py:46-55, structures/image_list.py:49-91); where the chain starts with a ColorJitter, at
+most two more launches per batch apply it to the decoded pixels first (csrc/color_jitter.hip, data/color_jitter.py).  The resize is Pillow's bilinear resample reproduced bit
 for bit (integer arithmetic), so the batch equals what the host transforms produce; ground-truth boxes are resized /
-mirrored by the same BoxList methods the reference calls.  Random decisions (training scale, flip) are drawn from
-Python's `random` in the reference's per-sample order: get_size, then the flip toss — by the preparer itself, or (the
+mirrored by the same BoxList methods the reference calls.  Random decisions (jitter, training scale, flips) are drawn from
+Python's `random` in the host chain's per-sample order (data/transforms.py draw_decisions) — by the preparer itself, or (the
 loaders of data/build.py with device_prep=True) inside the dataset's __getitem__, where the host chain draws them.
 `DevicePrepLoader` puts a raw DataLoader and a preparer behind the interface of the host loaders."""
 import collections
@@ -18,7 +19,8 @@ import torch
 from .. import _lib
 from ..structures.image_list import ImageList
 from .datasets import RainImage, RainyDataset, RawImage
-from .transforms import RandomHorizontalFlip, Resize, transform_params
+from .color_jitter import jitter_device
+from .transforms import build_transforms, draw_decisions, split_decision
 
 _PRECISION_BITS = 32 - 8 - 2
 _TABLES = {}
@@ -63,7 +65,7 @@ def _p(t):
 
 
 def resize_normalize_into(image_u8, out_hw, flip, mean, std, to_bgr255, out_slot):
-    """image_u8 [H,W,3] uint8 on the device -> writes fp32 into out_slot, a [3, Hp, Wp] channels_last view (physically
+    """image_u8 [H,W,3] uint8 on the device, flip a bool or a mask of _lib.FLIP_H / FLIP_V -> writes fp32 into out_slot, a [3, Hp, Wp] channels_last view (physically
     [Hp][Wp][3]) with Hp >= oh, Wp >= ow; everything outside [oh, ow] is left untouched (zero padding)"""
     if not image_u8.is_cuda:
         raise _lib.DadetError("resize_normalize_into: the image must live on the HIP device")
@@ -86,7 +88,7 @@ def resize_normalize_into(image_u8, out_hw, flip, mean, std, to_bgr255, out_slot
     assert out_slot.stride(0) == 1 and out_slot.stride(2) == 3, "out_slot must be a channels_last [3,Hp,Wp] view"
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _lib.call("dadet_image_resample_v_normalize", _p(cur), H, ow, _p(bh), _p(ch), kh, oh, int(bool(flip)),
+    _lib.call("dadet_image_resample_v_normalize", _p(cur), H, ow, _p(bh), _p(ch), kh, oh, int(flip),
               int(bool(to_bgr255)), m, s, _p(out_slot), int(out_slot.stride(1) // 3), stream)
 
 
@@ -95,26 +97,25 @@ class DeviceBatchPreparer(object):
     followed by `BatchCollator(cfg.DATALOADER.SIZE_DIVISIBILITY)`."""
 
     def __init__(self, cfg, is_train=True):
-        min_size, max_size, flip_prob = transform_params(cfg, is_train)
-        self.resize = Resize(min_size, max_size)
-        self.flip = RandomHorizontalFlip(flip_prob)
+        self.transforms = build_transforms(cfg, is_train)          # for its draws alone: nothing of it is applied
         self.mean, self.std = cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD
         self.to_bgr255 = cfg.INPUT.TO_BGR255
         self.size_divisible = cfg.DATALOADER.SIZE_DIVISIBILITY
 
     def __call__(self, images_u8, targets=None, decisions=None):
         """images_u8: list of uint8 [H,W,3] RGB device tensors, or of the loaders' `RawImage` (device pixels with the
-        decisions drawn in the dataset).  decisions (optional): list of ((oh, ow), flip) to use instead of those, or
-        instead of drawing them here."""
+        decisions drawn in the dataset).  decisions (optional): list of ((oh, ow), flip) or ((oh, ow), flip, vertical
+        flip, jitter operators) — data/transforms.py draw_decisions — to use instead of those, or instead of drawing them
+        here.  Images whose decision carries jitter operators are jittered on the current stream first."""
         if decisions is None and all(isinstance(im, RawImage) for im in images_u8):
             decisions = [im.decision for im in images_u8]
         images_u8 = [im.pixels if isinstance(im, RawImage) else im for im in images_u8]
         n = len(images_u8)
         if decisions is None:
             decisions = []
-            for img in images_u8:      # per sample: Resize.get_size first, then the flip toss (transforms/build.py:19-26)
-                size = self.resize.get_size((int(img.shape[1]), int(img.shape[0])))
-                decisions.append((size, self.flip.toss()))
+            # per sample, in the order of the chain's steps (transforms/build.py:36-45)
+            decisions = [draw_decisions(self.transforms, (int(img.shape[1]), int(img.shape[0]))) for img in images_u8]
+        images_u8 = jitter_device(images_u8, [split_decision(d)[3] for d in decisions])
         sizes = [d[0] for d in decisions]
         hp, wp = max(s[0] for s in sizes), max(s[1] for s in sizes)
         if self.size_divisible > 0:
@@ -132,16 +133,19 @@ class DeviceBatchPreparer(object):
         if targets is None:
             return None
         out = []
-        for t, ((oh, ow), flip) in zip(targets, decisions):
+        for t, decision in zip(targets, decisions):
+            (oh, ow), flip, vflip, _ = split_decision(decision)
             t = t.resize((ow, oh))
-            out.append(t.transpose(0) if flip else t)
+            t = t.transpose(0) if flip else t
+            out.append(t.transpose(1) if vflip else t)
         return out
 
 
 def prepare_batch_into(images_u8, decisions, mean, std, to_bgr255, batch):
-    """images_u8: uint8 [H,W,3] device tensors; decisions: ((oh, ow), flip) per image; batch: fp32 [n,3,Hp,Wp]
+    """images_u8: uint8 [H,W,3] device tensors; decisions: ((oh, ow), flip[, vertical flip, ...]) per image; batch: fp32 [n,3,Hp,Wp]
     channels_last on the same device, uninitialised.  One launch per _lib.IMAGE_BATCH_MAX images (dadet_image_prepare_batch)
-    on the current stream writes image i, resized / mirrored / normalised, into batch[i] and zeros around it."""
+    on the current stream writes image i, resized / mirrored / normalised, into batch[i] and zeros around it.  (The jitter
+    operators of a long decision are the caller's to apply: DeviceBatchPreparer does, ahead of this.)"""
     n, _, hp, wp = (int(v) for v in batch.shape)
     if not batch.is_cuda or any(not im.is_cuda for im in images_u8):
         raise _lib.DadetError("prepare_batch_into: images and batch must live on the HIP device")
@@ -157,14 +161,14 @@ def prepare_batch_into(images_u8, decisions, mean, std, to_bgr255, batch):
         count = min(_lib.IMAGE_BATCH_MAX, n - first)
         items = (_lib.ImageItem * count)()
         for j in range(count):
-            img, ((oh, ow), flip) = images_u8[first + j], decisions[first + j]
+            img, ((oh, ow), flip, vflip, _) = images_u8[first + j], split_decision(decisions[first + j])
             assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3 and img.device == dev
             img = img.contiguous()
             keep.append(img)
             H, W = int(img.shape[0]), int(img.shape[1])
             it = items[j]
             it.src, it.H, it.W, it.out_h, it.out_w = img.data_ptr(), H, W, int(oh), int(ow)
-            it.flip, it.slot = int(bool(flip)), first + j
+            it.flip, it.slot = (_lib.FLIP_H if flip else 0) | (_lib.FLIP_V if vflip else 0), first + j
             if ow != W:
                 bw, cw, it.h_ksize = _device_tables(W, int(ow), dev)
                 it.h_bounds, it.h_coeffs = bw.data_ptr(), cw.data_ptr()
@@ -211,7 +215,9 @@ class DevicePrepLoader(object):
 
     Samples of a RainyDataset (`RainImage`: source pixels + rain mask index + plan) become their rainy image on the side
     stream before the preparation launch (data/rain.py synthesize_device); pixels two samples share — an aligned triplet's
-    source and rainy sample — are copied and uploaded once."""
+    source and rainy sample — are copied and uploaded once.  The colour jitter of a sample's decision follows, on the same
+    stream and into a buffer of its own (the preparer applies it): the rainy sample is jittered as a rainy image, like on
+    the host chain, and two samples that share an upload may draw different jitters."""
 
     SIDE_STREAM = 3            # utils/streams.py: 0 / 1 bookkeeping sections, 2 the weight-gradient lane
 

@@ -478,7 +478,11 @@ int dadet_roi_pool_backward(const float* grad_output, const int* argmax, const f
  * memory); bounds [out][2] = (first input index, tap count) and coeffs [out][ksize] (22-bit fixed point) are Pillow's
  * per-axis tables (computed on the host, da_detect_amd/data/device_prep.py).  Pass 1 resamples rows to out_w and
  * rounds to 8 bits; pass 2 resamples columns (bounds NULL: none), optionally mirrors, converts and writes fp32
- * [out_h][out_row_stride][3] — a slot of the zero-filled padded batch tensor.  mean3 / std3 are HOST pointers. */
+ * [out_h][out_row_stride][3] — a slot of the zero-filled padded batch tensor.  mean3 / std3 are HOST pointers.
+ * flip is a bit mask (here and in dadet_image_item): DADET_FLIP_H mirrors the columns (RandomHorizontalFlip),
+ * DADET_FLIP_V writes output row out_h - 1 - y (RandomVerticalFlip); 0 .. 3. */
+#define DADET_FLIP_H 1
+#define DADET_FLIP_V 2
 int dadet_image_resample_h(const unsigned char* image_hwc, int H, int W, const int* bounds, const int* coeffs,
                            int ksize, int out_w, unsigned char* out_hwc, void* stream);
 int dadet_image_resample_v_normalize(const unsigned char* image_hwc, int in_h, int w, const int* bounds,
@@ -504,6 +508,37 @@ typedef struct dadet_image_item {
 } dadet_image_item;
 int dadet_image_prepare_batch(const dadet_image_item* items, int n, int to_bgr255, const float* mean3,
                               const float* std3, float* out, int n_slots, int Hp, int Wp, void* stream);
+
+/* Colour jitter (color_jitter.hip): torchvision's ColorJitter on its PIL back end — Pillow's ImageEnhance.Brightness /
+ * Contrast / Color and the HSV round trip of adjust_hue — restated in Pillow's 8-bit arithmetic, ahead of
+ * dadet_image_prepare_batch.  items: HOST array of n <= DADET_JITTER_BATCH_MAX descriptors (by value in the kernel
+ * arguments); src / out: uint8 [H][W][3] RGB device memory, 16-byte aligned, out a buffer of its own.  op[k] / factor[k],
+ * k < n_ops, are the operators in the order they are applied, each at most once; the hue operator reads hue_shift
+ * (0 .. 255, already  int(f * 255) mod 256) instead of its factor.  Per pixel, d the operator's degenerate value:
+ *   blend(d, x, a) = saturate_u8((int) f32(f32(d) + f32(a * f32(x - d))))      (Image.blend; exact d at a = 0, x at a = 1)
+ *   L = (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16
+ *   brightness d = 0;  saturation d = L;  contrast d = m = (2 * sum(L) + count) / (2 * count) over the image as it ENTERS
+ *   the contrast (after the operators in front of it);  hue: RGB -> HSV, h += hue_shift mod 256, HSV -> RGB (Convert.c).
+ * sums: device memory, one 64-bit word per descriptor (DADET_JITTER_BATCH_MAX of them serve any call), content before
+ * the call meaningless; afterwards its first words hold sum(L) of the descriptors with a contrast, in their order.  One 64-bit clear of `sums` and at most two launches serve the whole batch: a sum pass over
+ * the descriptors whose list holds the contrast (the operators in front of it per pixel in registers, L reduced per wave
+ * and workgroup, ONE 64-bit integer atomic add per workgroup: order-independent, so deterministic), then the apply pass.
+ * A descriptor with n_ops == 0 is skipped (its out is not written); nothing to do means no launch. */
+#define DADET_JITTER_BATCH_MAX 8
+#define DADET_JITTER_MAX_OPS 4
+#define DADET_JITTER_MAX_PIXELS (1 << 28)
+#define DADET_JITTER_BRIGHTNESS 0
+#define DADET_JITTER_CONTRAST 1
+#define DADET_JITTER_SATURATION 2
+#define DADET_JITTER_HUE 3
+typedef struct dadet_jitter_item {
+  const void* src;        /* uint8 [H][W][3] RGB */
+  void* out;              /* uint8 [H][W][3] RGB */
+  int H, W, n_ops, hue_shift;
+  int op[DADET_JITTER_MAX_OPS];
+  float factor[DADET_JITTER_MAX_OPS];
+} dadet_jitter_item;
+int dadet_color_jitter_batch(const dadet_jitter_item* items, int n, unsigned long long* sums, void* stream);
 
 /* Rain synthesis (rain.hip): the auxiliary rainy rendering of a source image from a rain-mask image, replacing the reference's
  * offline efficientderain-master/generate_rainy_cityscape.py (rain_aug -> augment_and_mix(severity 3, width 3) -> Pillow affine

@@ -1035,7 +1035,31 @@ def deform_sample_forward(x, offset, mask, kh, kw, stride, pad, dil, dg):
     return cols
 
 
-def deform_sample_backward(x, offset, mask, gcols, kh, kw, stride, pad, dil, dg, need_x=True):
+def _deform_workspace(N, H, W, dg, device, workspace):
+    """the per-cell sample lists of the gather form (csrc/deform.hip) -> (pointer, bytes); workspace=False: none, the call
+    of a C consumer of dadet_deform_sample_backward (the atomic forms run)"""
+    if not workspace:
+        return None, None, ctypes.c_size_t(0)
+    nbytes = ctypes.c_size_t(0)
+    _lib.call("dadet_deform_sample_backward_workspace_bytes", N, H, W, dg, ctypes.byref(nbytes))
+    ws = _workspace(nbytes.value, device)
+    return ws, _p(ws), ctypes.c_size_t(ws.numel())
+
+
+def deform_sample_backward_form(N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, workspace=True):
+    """which form of the sampling backward this geometry runs (no launch; the launcher's own choice):
+    0 the plain atomic kernel, 1 the LDS-window kernel, 2 the two-pass gather.  workspace as in deform_sample_backward"""
+    nbytes = ctypes.c_size_t(0)
+    if workspace:
+        _lib.call("dadet_deform_sample_backward_workspace_bytes", N, H, W, dg, ctypes.byref(nbytes))
+        nbytes = ctypes.c_size_t(max(nbytes.value, 16))
+    form = _lib.load().dadet_deform_sample_backward_form(N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, nbytes)
+    if form < 0:
+        _lib.check(form, "dadet_deform_sample_backward_form")
+    return form
+
+
+def deform_sample_backward(x, offset, mask, gcols, kh, kw, stride, pad, dil, dg, need_x=True, workspace=True):
     x, offset, gcols = _nhwc(x), _nhwc(offset), _nhwc(gcols)
     mask = _nhwc(mask) if mask is not None else None
     N, C, H, W = x.shape
@@ -1044,12 +1068,10 @@ def deform_sample_backward(x, offset, mask, gcols, kh, kw, stride, pad, dil, dg,
     gx = torch.empty_like(x).zero_() if need_x else None
     goffset = torch.empty_like(offset).zero_()
     gmask = torch.empty_like(mask).zero_() if mask is not None else None
-    nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_deform_sample_backward_workspace_bytes", N, H, W, dg, ctypes.byref(nbytes))
-    ws = _workspace(nbytes.value, x.device)      # per-cell sample lists of the gather form (csrc/deform.hip)
+    ws, ws_p, ws_bytes = _deform_workspace(N, H, W, dg, x.device, workspace)
     _lib.call("dadet_deform_sample_backward_ld", _p(x), _p(offset), dg * 2 * T, _p(mask), dg * T, 0, _p(gcols), _p(gx),
-              _p(goffset), dg * 2 * T, _p(gmask), dg * T, N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, _p(ws),
-              ctypes.c_size_t(ws.numel()), _stream())
+              _p(goffset), dg * 2 * T, _p(gmask), dg * T, N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, ws_p,
+              ws_bytes, _stream())
     return gx, goffset, gmask
 
 
@@ -1074,7 +1096,7 @@ def deform_sample_forward_om(x, om, kh, kw, stride, pad, dil, dg, modulated):
     return _amax.carry(cols, x)
 
 
-def deform_sample_backward_om(x, om, gcols, kh, kw, stride, pad, dil, dg, modulated):
+def deform_sample_backward_om(x, om, gcols, kh, kw, stride, pad, dil, dg, modulated, workspace=True):
     """-> (gx [N,C,H,W], gom [N, ld, Ho, Wo]): gradients w.r.t. the sampled map and w.r.t. the offset conv's output
     (offset channels, modulation logits; the padding channels stay zero)"""
     x, om, gcols = _nhwc(x), _nhwc(om), _nhwc(gcols)
@@ -1086,22 +1108,20 @@ def deform_sample_backward_om(x, om, gcols, kh, kw, stride, pad, dil, dg, modula
     flat = torch.zeros(x.numel() + om.numel(), dtype=torch.float32, device=x.device)
     gx = flat[:x.numel()].view(N, H, W, C).permute(0, 3, 1, 2)
     gom = flat[x.numel():].view(N, Ho, Wo, ld).permute(0, 3, 1, 2)
-    nbytes = ctypes.c_size_t(0)
-    _lib.call("dadet_deform_sample_backward_workspace_bytes", N, H, W, dg, ctypes.byref(nbytes))
-    ws = _workspace(nbytes.value, x.device)
+    ws, ws_p, ws_bytes = _deform_workspace(N, H, W, dg, x.device, workspace)
     if _mode4():
         # gom is an operand of the offset conv's weight-gradient GEMM: the pass that stores it leaves its largest magnitude
         # (one dadet_amax pass + its launch gap less per deformable block: 30 per step of R-101-FPN-DCN)
         slot = _amax.new_slot(x.device)
         _lib.call("dadet_deform_sample_backward_ld_m", _p(x), _p(om), ld, _off_ptr(om, 2 * T * dg) if modulated else None,
                   ld, 1, _p(gcols), _p(gx), _p(gom), ld, _off_ptr(gom, 2 * T * dg) if modulated else None, ld,
-                  N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, _p(ws), ctypes.c_size_t(ws.numel()),
+                  N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, ws_p, ws_bytes,
                   ctypes.c_void_p(slot[0]), ctypes.c_longlong(gom.numel()), _stream())
         _amax.attach(gom, slot)
         return gx, gom
     _lib.call("dadet_deform_sample_backward_ld", _p(x), _p(om), ld, _off_ptr(om, 2 * T * dg) if modulated else None, ld,
               1, _p(gcols), _p(gx), _p(gom), ld, _off_ptr(gom, 2 * T * dg) if modulated else None, ld,
-              N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, _p(ws), ctypes.c_size_t(ws.numel()), _stream())
+              N, H, W, C, kh, kw, stride, pad, dil, dg, Ho, Wo, ws_p, ws_bytes, _stream())
     return gx, gom
 
 

@@ -332,8 +332,9 @@ __global__ __launch_bounds__(256) void deform_sample_bwd_lds_kernel(const float*
 // 52 / 195 / 25.  A cell gathers from the four lists whose footprint covers it — top-left positions (y, x), (y, x-1), (y-1, x),
 // (y-1, x-1), as corner 0 .. 3 — and rebuilds its corner weight from (lh, lw) with the forward's own expression.
 // Lists hold kListCap entries (a regular 3x3 pattern puts 9 on a position); a sample that finds its list full is added to gx
-// directly with float atomics by pass A (gx is zero-filled by the caller).  The order of a list — hence the last bits of gx
-// — depends on the arrival order of the appends.
+// directly with float atomics by pass A (gx is zero-filled by the caller), summed first with the samples of the same wavefront
+// that overflow on the same position.  The order of a list — hence the last bits of gx — depends on the arrival order of the
+// appends.
 constexpr int kListCap = 32;
 
 struct ListEntry {
@@ -448,17 +449,61 @@ __global__ __launch_bounds__(256) void deform_sample_bwd_coord_kernel(const floa
             d_w[u] += ge * (hh * (b2[e] - b1[e]) + k[u].lh * (b4[e] - b3[e]));
             d_m[u] += g4[e] * (cw[u][0] * b1[e] + cw[u][1] * b2[e] + cw[u][2] * b3[e] + cw[u][3] * b4[e]);
           }
-          if (full[u]) {      // overflowed lists (rare): this pixel's corners go to gx directly
-            float* base = gimg + ((size_t)k[u].hl * g.W + k[u].wl) * g.C + c;
+        }
+      }
+      // Overflowed lists (rare; wave-uniform branch, outside the loop above so that it costs that loop no registers): the
+      // corners inside the map go to gx with float atomics.  A pile-up on one position is a serial float chain on four
+      // addresses — 1080 samples on one position: 1048 adds, whose rounding came to 4.9x that of the float32 oracle's blocked
+      // sum (1.7e-6 of the maximum) — and the samples of a pile-up sit next to each other.  So the wavefront's 4 pixels x 3
+      // taps that go to the SAME position are summed first (pairs of pixels, pairs of pairs, then the taps) and one of them
+      // sends the sum: up to 12x fewer adds on the chain, the rest of the sum a tree.
+      if (g.ablate != 2 && __any((full[0] | full[1] | full[2]) != 0)) {
+        for (int c = grp * cpg + l16 * 4; c < (grp + 1) * cpg; c += kDChunk) {
+          float v[3][16];       // [tap][corner * 4 + channel]
+          unsigned f[3];        // the corners this lane still has to send
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float ge = g4[e] * mk[u];
-              if (full[u] & 1u) unsafeAtomicAdd(base + e, cw[u][0] * ge);
-              if (full[u] & 2u) unsafeAtomicAdd(base + g.C + e, cw[u][1] * ge);
-              if (full[u] & 4u) unsafeAtomicAdd(base + (size_t)g.W * g.C + e, cw[u][2] * ge);
-              if (full[u] & 8u) unsafeAtomicAdd(base + (size_t)g.W * g.C + g.C + e, cw[u][3] * ge);
+          for (int u = 0; u < 3; ++u) {
+            f[u] = full[u];
+            const float4 gv = buf_load4(gr, f[u] ? (unsigned)((m * T + tap0 + u) * g.C + c) * 4u : kOOB);
+            const float g4[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) v[u][q * 4 + e] = cw[u][q] * (g4[e] * mk[u]);
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {      // the same tap of the other pixels (all 16 lanes of a pixel agree)
+              const unsigned pf = (unsigned)__shfl_xor((int)f[u], o, 64);
+              const int phl = __shfl_xor(k[u].hl, o, 64), pwl = __shfl_xor(k[u].wl, o, 64);
+              const bool same = f[u] && pf && phl == k[u].hl && pwl == k[u].wl;     // (hence the same corners inside the map)
+#pragma unroll
+              for (int i = 0; i < 16; ++i) {
+                const float pv = __shfl_xor(v[u][i], o, 64);
+                if (same && !(lane & o)) v[u][i] += pv;
+              }
+              if (same && (lane & o)) f[u] = 0;       // the partner sends this sample's share
             }
           }
+#pragma unroll
+          for (int u = 1; u < 3; ++u)
+#pragma unroll
+            for (int t = 0; t < u; ++t)
+              if (f[u] && f[t] && k[u].hl == k[t].hl && k[u].wl == k[t].wl) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) v[t][i] += v[u][i];
+                f[u] = 0;
+              }
+#pragma unroll
+          for (int u = 0; u < 3; ++u)
+            if (f[u]) {
+              float* base = gimg + ((size_t)k[u].hl * g.W + k[u].wl) * g.C + c;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                if (f[u] & 1u) unsafeAtomicAdd(base + e, v[u][e]);
+                if (f[u] & 2u) unsafeAtomicAdd(base + g.C + e, v[u][4 + e]);
+                if (f[u] & 4u) unsafeAtomicAdd(base + (size_t)g.W * g.C + e, v[u][8 + e]);
+                if (f[u] & 8u) unsafeAtomicAdd(base + (size_t)g.W * g.C + g.C + e, v[u][12 + e]);
+              }
+            }
         }
       }
 #pragma unroll
@@ -585,11 +630,11 @@ static bool al16d(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) 
 
 static int deform_sample_forward_impl(const float* x, const float* offset, const float* mask, float* cols, DeformGeom g,
                                       void* stream) {
-  const int lanes = g.C / 4;
-  const int threads = (lanes < 256 && 256 % lanes == 0) ? 256 : ((lanes >= 256) ? 256 : ((lanes + 63) / 64) * 64);
-  const int ppb = (lanes < threads && threads % lanes == 0) ? threads / lanes : 1;      // output pixels per workgroup
   int rc = deform_check("deform_sample_forward", g.N, g.H, g.W, g.C, g.KH, g.KW, g.stride, g.pad, g.dil, g.dg, g.Ho, g.Wo);
   if (rc) return rc;
+  const int lanes = g.C / 4;      // >= 1 past the check (C < 4 would make the remainders below divide by zero)
+  const int threads = (lanes < 256 && 256 % lanes == 0) ? 256 : ((lanes >= 256) ? 256 : ((lanes + 63) / 64) * 64);
+  const int ppb = (lanes < threads && threads % lanes == 0) ? threads / lanes : 1;      // output pixels per workgroup
   if (g.N == 0) return DADET_OK;
   DADET_REQUIRE(x && offset && cols && al16d(x) && al16d(cols), "deform_sample_forward: bad pointers");
   const int T = g.KH * g.KW;
@@ -616,6 +661,24 @@ extern "C" int dadet_deform_sample_forward_ld(const float* x, const float* offse
   return deform_sample_forward_impl(x, offset, mask, cols, g, stream);
 }
 
+static size_t deform_lists(const DeformGeom& g) { return (size_t)g.N * (g.H + 1) * (g.W + 1) * g.dg; }
+static size_t deform_workspace_need(size_t lists) { return lists * sizeof(int) + 256 + lists * kListCap * sizeof(ListEntry); }
+
+// Which form of the backward serves a problem (past deform_check): 0 the plain atomic kernel, 1 the LDS-window kernel,
+// 2 the two-pass gather.  The launcher and the query dadet_deform_sample_backward_form both ask here.  `aligned`: x, gcols,
+// gx and the workspace are 16-byte aligned.  DADET_DEFORM_BWD_LDS (read once per process): "0" never the LDS-window or the
+// gather form, "1" the LDS-window kernel where the gather form would run.
+static int deform_backward_form(const DeformGeom& g, bool has_workspace, size_t workspace_bytes, bool aligned) {
+  static const bool allow_lds = !(getenv("DADET_DEFORM_BWD_LDS") && getenv("DADET_DEFORM_BWD_LDS")[0] == '0');
+  static const bool window = getenv("DADET_DEFORM_BWD_LDS") && getenv("DADET_DEFORM_BWD_LDS")[0] == '1';
+  if (!(allow_lds && g.stride == 1 && g.dil * (g.KH - 1) <= 2 && g.dil * (g.KW - 1) <= 2 && g.C % kDChunk == 0)) return 0;
+  const int T = g.KH * g.KW;
+  const bool gather = !window && has_workspace && workspace_bytes >= deform_workspace_need(deform_lists(g)) &&
+                      ((g.C / g.dg) % kDChunk) == 0 && aligned &&
+                      (uint64_t)g.N * g.Ho * g.Wo * T * g.C * 4 < 0xFFFFFFF0ull && (uint64_t)g.N * g.Ho * g.Wo * T < 0xFFFFFFFFull;
+  return gather ? 2 : 1;
+}
+
 static int deform_sample_backward_impl(const float* x, const float* offset, const float* mask, const float* gcols,
                                        float* gx, float* goffset, float* gmask, DeformGeom g, void* workspace,
                                        size_t workspace_bytes, void* stream, unsigned* amax_g = nullptr,
@@ -631,19 +694,16 @@ static int deform_sample_backward_impl(const float* x, const float* offset, cons
   DADET_REQUIRE(g.off_ld >= g.dg * 2 * T && g.goff_ld >= g.dg * 2 * T && (!mask || g.mask_ld >= g.dg * T) &&
                     (!gmask || g.gmask_ld >= g.dg * T),
                 "deform_sample_backward: row stride too small");
-  static const bool allow_lds = !(getenv("DADET_DEFORM_BWD_LDS") && getenv("DADET_DEFORM_BWD_LDS")[0] == '0');
-  if (allow_lds && g.stride == 1 && g.dil * (g.KH - 1) <= 2 && g.dil * (g.KW - 1) <= 2 && g.C % kDChunk == 0) {
+  const bool aligned = (((uintptr_t)x | (uintptr_t)gcols | (uintptr_t)gx | (uintptr_t)workspace) & 15) == 0;
+  const int form = deform_backward_form(g, workspace != nullptr, workspace_bytes, aligned);
+  if (form != 0) {
     const int tiles_x = ceil_div(g.Wo, kDTile), tiles_y = ceil_div(g.Ho, kDTile);
     const size_t lds = sizeof(float) * kDWin * kDWin * kDChunk;
     static bool attr_set = false;
     if (const int rc = raise_lds_once(&attr_set, "deform_sample_backward", deform_sample_bwd_lds_kernel, lds); rc != DADET_OK)
       return rc;
-    static const bool window = getenv("DADET_DEFORM_BWD_LDS") && getenv("DADET_DEFORM_BWD_LDS")[0] == '1';
-    const size_t lists = (size_t)g.N * (g.H + 1) * (g.W + 1) * g.dg;
-    const size_t need = lists * sizeof(int) + 256 + lists * kListCap * sizeof(ListEntry);
-    if (!window && workspace && workspace_bytes >= need && ((g.C / g.dg) % kDChunk) == 0 &&
-        (((uintptr_t)x | (uintptr_t)gcols | (uintptr_t)gx | (uintptr_t)workspace) & 15) == 0 &&
-        (uint64_t)g.N * g.Ho * g.Wo * T * g.C * 4 < 0xFFFFFFF0ull && (uint64_t)g.N * g.Ho * g.Wo * T < 0xFFFFFFFFull) {
+    if (form == 2) {
+      const size_t lists = deform_lists(g);
       int* counts = static_cast<int*>(workspace);
       ListEntry* entries = reinterpret_cast<ListEntry*>(static_cast<char*>(workspace) + ((lists * sizeof(int) + 255) & ~(size_t)255));
       if (gx) (void)hipMemsetAsync(counts, 0, lists * sizeof(int), as_stream(stream));
@@ -681,9 +741,15 @@ extern "C" int dadet_deform_sample_backward(const float* x, const float* offset,
 
 extern "C" int dadet_deform_sample_backward_workspace_bytes(int N, int H, int W, int deformable_groups, size_t* bytes_out) {
   DADET_REQUIRE(N >= 0 && H > 0 && W > 0 && deformable_groups > 0 && bytes_out, "deform_sample_backward_workspace_bytes: bad args");
-  const size_t lists = (size_t)N * (H + 1) * (W + 1) * deformable_groups;
-  *bytes_out = lists * sizeof(int) + 256 + lists * kListCap * sizeof(ListEntry);
+  *bytes_out = deform_workspace_need((size_t)N * (H + 1) * (W + 1) * deformable_groups);
   return DADET_OK;
+}
+
+extern "C" int dadet_deform_sample_backward_form(int N, int H, int W, int C, int KH, int KW, int stride, int pad, int dil,
+                                                 int deformable_groups, int Ho, int Wo, size_t workspace_bytes) {
+  if (deform_check("deform_sample_backward_form", N, H, W, C, KH, KW, stride, pad, dil, deformable_groups, Ho, Wo)) return -1;
+  DeformGeom g{N, H, W, C, KH, KW, stride, pad, dil, deformable_groups, Ho, Wo};
+  return deform_backward_form(g, workspace_bytes > 0, workspace_bytes, true);
 }
 
 extern "C" int dadet_deform_sample_backward_ld(const float* x, const float* offset, int offset_ld, const float* mask,

@@ -462,6 +462,15 @@ int dadet_deform_sample_backward_ld_m(const float* x, const float* offset, int o
 /* scratch for the gather form of the backward (per-cell lists of the samples whose bilinear corners land on a cell:
  * csrc/deform.hip); without it (NULL / too small) the atomic forms run */
 int dadet_deform_sample_backward_workspace_bytes(int N, int H, int W, int deformable_groups, size_t* bytes_out);
+/* which form of the backward a call with this geometry and a workspace of `workspace_bytes` (0: none) runs; launches
+ * nothing and shares the launcher's own choice: 0 = the plain atomic kernel, 1 = the LDS-window kernel (stride 1, kernel
+ * extent <= 3, C % 64 == 0), 2 = the two-pass gather (also: whole 64-channel chunks per deformable group, a workspace of
+ * at least dadet_deform_sample_backward_workspace_bytes, 32-bit extents); -1 for a geometry the operators refuse.
+ * The data pointers are taken as 16-byte aligned (as torch allocates them).  dadet_deform_sample_backward passes no
+ * workspace.  DADET_DEFORM_BWD_LDS (an A/B switch, read once per process): 0 = always the plain kernel, 1 = the
+ * LDS-window kernel in place of the gather. */
+int dadet_deform_sample_backward_form(int N, int H, int W, int C, int KH, int KW, int stride, int pad, int dil,
+                                      int deformable_groups, int Ho, int Wo, size_t workspace_bytes);
 
 /* ROIPool — replaces `_C.roi_pool_forward / roi_pool_backward` (csrc/vision.cpp:11-12, ROIPool.h:11-46,
  * cuda/ROIPool_cuda.cu:16-108).  input [B][H][W][C] NHWC, rois [R][5] = (batch, x1, y1, x2, y2), output and

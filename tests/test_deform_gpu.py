@@ -151,20 +151,37 @@ def test_deform_conv_matches_second_oracle_on_border_cases(device, cfg):
         assert err < 2e-4, "grad %s: %.3e" % (name, err)
 
 
+# the form of the sampling backward each case below runs (csrc/deform.hip, as dadet_deform_sample_backward_form names them:
+# 0 plain atomic kernel, 1 LDS window, 2 two-pass gather); the wrappers always pass the gather form's workspace
+MATCHES_ORACLE_FORMS = {
+    # fewer than 64 channels, stride 2: the plain kernel
+    (2, 16, 9, 11, 24, 3, 1, 1, False): 0, (2, 32, 12, 10, 16, 3, 1, 1, True): 0, (1, 64, 15, 13, 32, 3, 2, 2, True): 0,
+    (2, 8, 7, 7, 8, 1, 1, 1, True): 0,
+    # stride 1, C % 64 == 0 and whole 64-channel chunks per deformable group: the gather (4 groups of 256; ragged maps with
+    # 1 group and with 2 groups of 64)
+    (1, 1024, 6, 7, 8, 3, 1, 4, True): 2, (2, 64, 20, 19, 16, 3, 1, 1, True): 2, (1, 128, 9, 17, 8, 3, 1, 2, False): 2,
+    # 4 groups of 16 channels (lanes of one chunk in different deformable groups): the LDS-window kernel
+    (1, 64, 10, 10, 8, 3, 1, 4, True): 1,
+}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", [(2, 16, 9, 11, 24, 3, 1, 1, False), (2, 32, 12, 10, 16, 3, 1, 1, True),
                                  (1, 64, 15, 13, 32, 3, 2, 2, True), (1, 1024, 6, 7, 8, 3, 1, 4, True),
                                  (2, 8, 7, 7, 8, 1, 1, 1, True),
-                                 # LDS-window backward (stride 1, C % 64 == 0): ragged tiles, 2 groups, and 4 groups of
-                                 # 16 channels (lanes of one chunk in different deformable groups)
+                                 # stride 1, C % 64 == 0: the gather form twice (ragged maps, 1 and 2 groups), then the
+                                 # LDS-window backward (4 groups of 16 channels); MATCHES_ORACLE_FORMS above
                                  (2, 64, 20, 19, 16, 3, 1, 1, True), (1, 128, 9, 17, 8, 3, 1, 2, False),
                                  (1, 64, 10, 10, 8, 3, 1, 4, True)])
 def test_deform_conv_matches_oracle(device, cfg):
+    from da_detect_amd import _C
     from da_detect_amd.layers.dcn import deform_conv, modulated_deform_conv
     from oracle import deform_ref as R
 
     N, C, H, W, Cout, k, stride, dg, modulated = cfg
     x, off, mask, w, b, pad = _case(sum(cfg[:7]), N, C, H, W, Cout, k, stride, dg, modulated)
+    form = _C.deform_sample_backward_form(N, H, W, C, k, k, stride, pad, 1, dg, off.shape[2], off.shape[3])
+    assert form == MATCHES_ORACLE_FORMS[cfg], "the case runs backward form %d, not the one it is here for" % form
     leaves = [t.clone().requires_grad_(True) for t in (x, off, w)] + \
         ([mask.clone().requires_grad_(True), b.clone().requires_grad_(True)] if modulated else [])
     want = R.deform_conv2d(leaves[0], leaves[1], leaves[3] if modulated else None, leaves[2],

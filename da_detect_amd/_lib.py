@@ -90,6 +90,17 @@ class JitterItem(ctypes.Structure):
         ("op", c_int * JITTER_MAX_OPS), ("factor", c_float * JITTER_MAX_OPS)]
 
 
+OVERLAY_BATCH_MAX = 8        # DADET_OVERLAY_BATCH_MAX
+OVERLAY_MAX_RECORDS = 1024   # DADET_OVERLAY_MAX_RECORDS
+OVERLAY_MAX_LABEL = 64       # DADET_OVERLAY_MAX_LABEL
+
+
+class OverlayItem(ctypes.Structure):
+    """mirror of dadet_overlay_item (include/dadet.h)"""
+
+    _fields_ = [("image", c_void_p)] + [(n, c_int) for n in ("H", "W", "first", "count")]
+
+
 # name -> argtypes ; every function returns int (status) unless listed in _RESTYPES
 _P = c_void_p
 _SIGNATURES = {
@@ -166,6 +177,7 @@ _SIGNATURES = {
     "dadet_image_prepare_batch": [POINTER(ImageItem), c_int, c_int, POINTER(c_float), POINTER(c_float), _P, c_int, c_int,
                                   c_int, _P],
     "dadet_color_jitter_batch": [POINTER(JitterItem), c_int, _P, _P],
+    "dadet_overlay_batch": [POINTER(OverlayItem), c_int, _P, _P, _P, _P],
     "dadet_rain_scratch_bytes": [c_int, c_int, c_int, POINTER(c_size_t)],
     "dadet_rain_synthesize": [_P, _P, c_int, c_int, c_int, POINTER(ctypes.c_double), POINTER(c_float), c_float, c_float, _P, _P,
                               c_size_t, _P],

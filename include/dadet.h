@@ -549,6 +549,38 @@ typedef struct dadet_jitter_item {
 } dadet_jitter_item;
 int dadet_color_jitter_batch(const dadet_jitter_item* items, int n, unsigned long long* sums, void* stream);
 
+/* Detections drawn onto images (overlay.hip; rules and host statement: da_detect_amd/engine/overlay.py), in
+ * place of the cv2.rectangle / cv2.putText calls of the reference's demo/predictor.py.  items: HOST array of
+ * n <= DADET_OVERLAY_BATCH_MAX descriptors (by value in the kernel arguments); image: uint8 [H][W][3] RGB device memory
+ * at any byte alignment, drawn IN PLACE with records [first, first + count) of `records`, count <= DADET_OVERLAY_MAX_RECORDS.
+ * records: device int32 [total][DADET_OVERLAY_RECORD_INTS] =
+ *   x0 y0 x1 y1 (inclusive corners, anywhere within +-2^30)  rgb (r | g << 8 | b << 16)  w (outline, clamped to 1 .. 8)
+ *   a (fill opacity 0 .. 256)  tx ty (origin of the label's first 6 x 11 cell)  text_offset  text_length (clamped to
+ *   0 .. DADET_OVERLAY_MAX_LABEL)  0
+ * text: device bytes, a record's label at text[text_offset .. + text_length) (a byte outside 0x20 .. 0x7e draws as `?`);
+ * glyphs: device uint8 [95][11], a row per byte, bit 5 the leftmost of 6 columns.  Per pixel, records in order, c the colour:
+ *   pass A  tint: a > 0 and inside the box: v = (c * a + v * (256 - a) + 128) >> 8;  outline: inside the box and
+ *           (x - x0 < w or x1 - x < w or y - y0 < w or y1 - y < w): v = c
+ *   pass B  (after ALL of pass A; records with text_length > 0)  plate: tx - 1 <= x <= tx + 6 * len and
+ *           ty - 1 <= y <= ty + 11: v = c;  ink: the glyph bit of character (x - tx) / 6 at ((x - tx) % 6, y - ty) is set:
+ *           v = white when (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16 < 128, else black
+ * One launch: a workgroup per 16 x 64 pixel tile of every image with records.  It culls the image's records against its
+ * tile DADET_OVERLAY_CHUNK at a time into an LDS list that keeps their order (ballot + prefix, no atomics) and applies the
+ * list to its pixels in registers, one walk over the records per pass; a tile nothing reaches is neither read nor written,
+ * and a thread stores its four pixels only when a record reached them.  Integer arithmetic, one owner per pixel: exact and independent of timing. */
+#define DADET_OVERLAY_BATCH_MAX 8
+#define DADET_OVERLAY_MAX_RECORDS 1024
+#define DADET_OVERLAY_MAX_LABEL 64
+#define DADET_OVERLAY_RECORD_INTS 12
+#define DADET_OVERLAY_CHUNK 256
+#define DADET_OVERLAY_MAX_PIXELS (1 << 28)
+typedef struct dadet_overlay_item {
+  void* image;            /* uint8 [H][W][3] RGB */
+  int H, W, first, count;
+} dadet_overlay_item;
+int dadet_overlay_batch(const dadet_overlay_item* items, int n, const int* records, const unsigned char* text,
+                        const unsigned char* glyphs, void* stream);
+
 /* Rain synthesis (rain.hip): the auxiliary rainy rendering of a source image from a rain-mask image, replacing the reference's
  * offline efficientderain-master/generate_rainy_cityscape.py (rain_aug -> augment_and_mix(severity 3, width 3) -> Pillow affine
  * warps -> screen blend -> 8-bit image).  image_hwc / mask_hwc / out_hwc: uint8 [H][W][3] RGB, device memory, the mask

@@ -344,6 +344,44 @@ def voc_match(det_box, gt_box, gt_difficult, det_off, gt_off, iou_thr):
     return match, n_pos, gt_index, iou_max
 
 
+def error_match_workspace_bytes(det_off, gt_off, n_det, n_gt):
+    """scratch of error_match for these per-image offset tables; validates them on the host exactly as the launch does"""
+    d_host, g_host, images = _pair_tables("error_match", det_off, gt_off)
+    return _query_bytes("dadet_error_match_workspace_bytes", d_host, g_host, images, int(n_det), int(n_gt))
+
+
+def error_match(det_box, det_label, gt_box, gt_label, gt_difficult, det_off, gt_off, pos_thresh=0.5, bg_thresh=0.1):
+    """Error kind of every detection in one launch, one workgroup per image (dadet_error_match): det_box [Nd, 4] /
+    gt_box [Ng, 4] xyxy float32, det_label [Nd] / gt_label [Ng] int32, gt_difficult [Ng] uint8 on the device; det_off / gt_off
+    host ints [images + 1] (image i's slices; detections best first, any number) ->
+    (det_kind uint8 [Nd], det_gt int32 [Nd], iou_same float32 [Nd], iou_other float32 [Nd], det_fix uint8 [Nd],
+    gt_state uint8 [Ng], gt_det int32 [Ng]) on the device."""
+    det_box = _dev(det_box, "det_box").contiguous()
+    det_label = _dev(det_label, "det_label", torch.int32).contiguous()
+    gt_box = _dev(gt_box, "gt_box").contiguous()
+    gt_label = _dev(gt_label, "gt_label", torch.int32).contiguous()
+    gt_difficult = _dev(gt_difficult, "gt_difficult", torch.uint8).contiguous()
+    n_det, n_gt = int(det_box.shape[0]), int(gt_box.shape[0])
+    if (det_box.numel() != 4 * n_det or gt_box.numel() != 4 * n_gt or det_label.numel() != n_det or gt_label.numel() != n_gt
+            or gt_difficult.numel() != n_gt):
+        raise _lib.DadetError("error_match: boxes must be [n, 4], det_label [n_det], gt_label and gt_difficult [n_gt]")
+    d_host, g_host, images = _pair_tables("error_match", det_off, gt_off)
+    dev = det_box.device
+    ws = _workspace(_query_bytes("dadet_error_match_workspace_bytes", d_host, g_host, images, n_det, n_gt), dev)
+    det_kind = torch.empty(n_det, dtype=torch.uint8, device=dev)
+    det_gt = torch.empty(n_det, dtype=torch.int32, device=dev)
+    iou_same = torch.empty(n_det, dtype=torch.float32, device=dev)
+    iou_other = torch.empty(n_det, dtype=torch.float32, device=dev)
+    det_fix = torch.empty(n_det, dtype=torch.uint8, device=dev)
+    gt_state = torch.empty(n_gt, dtype=torch.uint8, device=dev)
+    gt_det = torch.empty(n_gt, dtype=torch.int32, device=dev)
+    _lib.call("dadet_error_match", _p(det_box), _p(det_label), _p(gt_box), _p(gt_label), _p(gt_difficult), d_host, g_host, images,
+              n_det, n_gt, ctypes.c_double(float(pos_thresh)), ctypes.c_double(float(bg_thresh)), _p(ws),
+              ctypes.c_size_t(ws.numel()), _p(det_kind), _p(det_gt), _p(iou_same), _p(iou_other), _p(det_fix), _p(gt_state),
+              _p(gt_det), _stream())
+    return det_kind, det_gt, iou_same, iou_other, det_fix, gt_state, gt_det
+
+
 def nms(dets, scores, threshold):
     """_C.nms(dets[N,4], scores[N], thr) -> int64[K] kept original indices, ascending (nms.h:10-28)."""
     if dets.numel() == 0:

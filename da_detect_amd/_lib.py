@@ -119,6 +119,9 @@ _SIGNATURES = {
     "dadet_voc_match_workspace_bytes": [POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_size_t)],
     "dadet_voc_match": [_P, _P, _P, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(ctypes.c_double), c_int, _P,
                         c_size_t, _P, _P, _P, _P, _P],
+    "dadet_error_match_workspace_bytes": [POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(c_size_t)],
+    "dadet_error_match": [_P, _P, _P, _P, _P, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, ctypes.c_double,
+                          ctypes.c_double, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P],
     "dadet_roi_align_forward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_backward": [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P],
     "dadet_roi_align_workspace_bytes": [c_int, c_int, c_int, c_int, POINTER(c_size_t)],

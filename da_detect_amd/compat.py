@@ -38,6 +38,7 @@ _RELOCATED = {
     "data.datasets.evaluation.coco.coco_eval": "data.evaluation.coco.coco_eval",
     "data.datasets.evaluation.voc": "data.evaluation.voc",
     "data.datasets.evaluation.voc.voc_eval": "data.evaluation.voc.voc_eval",
+    "data.datasets.evaluation.errors": "data.evaluation.errors",      # not in the reference: the error breakdown
 }
 
 

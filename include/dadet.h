@@ -150,6 +150,32 @@ int dadet_voc_match(const float* det_box, const float* gt_box, const unsigned ch
                     float* iou_max_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Error breakdown of detections — every detection of a dataset gets the kind of its error, in ONE launch, one workgroup per
+ *   IMAGE (all classes at once; DESIGN.md 3k states the rule, which is this project's own statement of the TIDE breakdown on
+ *   top of the VOC matching rule above).
+ * Image i holds detections det_off_host[i] .. det_off_host[i+1] (any number, already in descending score) and ground truths
+ * gt_off_host[i] .. gt_off_host[i+1] (annotation order).  Boxes are xyxy float32, labels int32, gt_difficult uint8; the IoU is
+ * dadet_voc_match's float32 "+1" expression, bit for bit, and "v >= t" is !((double)v < t).  0 < bg_thr < pos_thr <= 1.
+ * Per detection three maxima (first maximum wins; 0.0 and no index without a candidate): cand over the ground truths of its
+ * class, s over the non-difficult ones of its class, o over the non-difficult ones of every other class.
+ * det_kind uint8 [n_det]: 1 ignored (cand difficult, IoU(cand) >= pos) | 0 TP (IoU(cand) >= pos, cand not difficult, smallest
+ * detection index with that cand — exactly dadet_voc_match's 1 at pos_thr) | else the first that holds of 3 Loc (bg <= s < pos),
+ * 2 Cls (o >= pos), 5 Dupe (s >= pos), 6 Bkg (s < bg and o < bg), 4 Both.  det_gt int32 [n_det]: index into gt_box of cand
+ * (TP, ignored, Dupe), argmax s (Loc), argmax o (Cls, Both), -1 (Bkg).  iou_same = s, iou_other = o, float32 [n_det].
+ * det_fix uint8 [n_det]: 1 for the smallest-index Loc (separately: Cls) detection of a ground truth without TP, else 0.
+ * gt_state uint8 [n_gt]: 0 detected (gt_det int32 = index of its TP detection; -1 in every other state), 1 difficult, 2 covered
+ * (no TP, but the det_gt of a Loc or Cls detection), 3 missed.  Offset tables, workspace and LDS as for dadet_voc_match
+ * (33 bytes per ground truth: box, label, three claim words, difficult byte).  Integer atomicMin only.
+ * ----------------------------------------------------------------------------------------------*/
+int dadet_error_match_workspace_bytes(const int* det_off_host, const int* gt_off_host, int images, int n_det, int n_gt,
+                                      size_t* bytes_out);
+int dadet_error_match(const float* det_box, const int* det_label, const float* gt_box, const int* gt_label,
+                      const unsigned char* gt_difficult, const int* det_off_host, const int* gt_off_host, int images, int n_det,
+                      int n_gt, double pos_thr, double bg_thr, void* workspace, size_t workspace_bytes, unsigned char* det_kind,
+                      int* det_gt, float* iou_same, float* iou_other, unsigned char* det_fix, unsigned char* gt_state,
+                      int* gt_det, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * ROIAlign — replaces `_C.roi_align_forward` / `_C.roi_align_backward`
  *   reference: csrc/ROIAlign.h:11-45, csrc/cpu/ROIAlign_cpu.cpp:114-257, csrc/cuda/ROIAlign_cuda.cu:65-254.
  * input  [B][H][W][C] NHWC, rois [R][5] = (batch_idx, x1, y1, x2, y2), output [R][PH][PW][C] NHWC.

@@ -30,6 +30,16 @@ written to `<output-dir>/<ROOT's name>_<SPLIT and options>.json` first and that 
 tools/test_net_da.py (which takes annotation files) evaluates: `predictions.pth` lands in the folder of that name under
 `<output-dir>/inference/`.
 
+`--errors [--bg-iou 0.1]` adds, after the scoring, the error breakdown of the detections (every image's classes
+matched at once on the device): per class and over all classes the detections by kind (TP, ignored, Cls, Loc, Both, Dupe,
+Bkg), the missed ground truths, AP and the AP that fixing each kind alone would return, at `--voc-iou`'s first value, with
+the 11-point metric unless `--metric voc12`; `errors.txt` and `errors.json` land next to the predictions.  It takes any of the
+three kinds of set.  `--errors --compare OTHER/predictions.pth` logs a second table for that file and the difference per
+kind: what adaptation fixed.
+
+    python tools/score_net_da.py --dataset ann.json,imgdir --predictions noadapt/predictions.pth --metric voc07 --errors \\
+        [--bg-iou 0.1] [--compare adapted/predictions.pth]
+
 `--device-prep` (with `--config-file`): the evaluation pass runs in this process as well, for either kind of set, fed from the
 device input pipeline — test-time augmentation through `TEST.BBOX_AUG.ENABLED True` included."""
 import argparse
@@ -91,7 +101,7 @@ def _evaluation_pass(args, folder):
               evaluate=lambda **_: None)      # scored below, from the saved file
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="COCO box AP / proposal recall of saved predictions, on MI355X")
     ap.add_argument("--dataset", type=_pair, required=True,
                     help="annotation.json,image_root of the test set — or voc:DIR,SPLIT, or "
@@ -110,8 +120,48 @@ def main():
                     help="with --config-file: the evaluation pass runs in this process (one GPU) and prepares its batches — and, "
                          "with TEST.BBOX_AUG.ENABLED True, every augmentation pass — on the device from decoded uint8 pixels "
                          "(data/device_prep.py); same inputs as the host transforms, bit for bit")
+    ap.add_argument("--errors", action="store_true",
+                    help="after the scoring: the error breakdown of the detections (kinds, missed, dAP per fix) at --voc-iou's "
+                         "first value, 11-point metric unless --metric voc12; writes errors.txt and errors.json")
+    ap.add_argument("--bg-iou", type=float, default=0.1, help="with --errors: below this IoU a detection touches nothing")
+    ap.add_argument("--compare", default=None, metavar="PREDICTIONS",
+                    help="with --errors: a second predictions.pth of the same set; its table and the differences are logged")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE overrides of the yaml (with --config-file)")
-    args = ap.parse_args()
+    return ap
+
+
+def _error_tables(args, dataset, predictions, folder, log):
+    """--errors: the breakdown of `predictions` (written next to them), then that of --compare and what changed"""
+    from da_detect_amd.data.evaluation import errors
+
+    settings = dict(pos_thresh=args.voc_iou[0], bg_thresh=args.bg_iou, use_07_metric=args.metric != "voc12")
+    first = errors.do_error_analysis(dataset, predictions, folder, log, **settings)
+    if args.compare is None:
+        return
+    other = torch.load(args.compare, weights_only=False)
+    if len(other) != len(dataset):
+        raise SystemExit("%s: %d predictions for %d images: not this dataset's predictions.pth" % (args.compare, len(other), len(dataset)))
+    log.info("--compare %s", args.compare)
+    second = errors.do_error_analysis(dataset, other, None, log, **settings)
+    rows = ["{:<8}{:>12}{:>12}{:>12}".format("", "predictions", "compare", "difference")]
+    for k, name in enumerate(errors.KIND_NAMES):
+        a, b = int(first["counts"][1:, k].sum()), int(second["counts"][1:, k].sum())
+        rows.append("{:<8}{:>12d}{:>12d}{:>+12d}".format(name, a, b, b - a))
+    a, b = int(first["missed"][1:].sum()), int(second["missed"][1:].sum())
+    rows.append("{:<8}{:>12d}{:>12d}{:>+12d}".format("missed", a, b, b - a))
+    rows.append("{:<8}{:>12.4f}{:>12.4f}{:>+12.4f}".format("mAP", first["map"], second["map"], second["map"] - first["map"]))
+    for name in errors.FIXES:
+        a, b = first["dap"][name], second["dap"][name]
+        rows.append("{:<8}{:>+12.4f}{:>+12.4f}{:>+12.4f}".format("d" + name, a, b, b - a))
+    log.info("what changed (compare - predictions)\n%s", "\n".join(rows))
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.compare is not None and not args.errors:
+        raise SystemExit("--compare goes with --errors")
+    if args.errors and args.proposals:
+        raise SystemExit("--errors breaks down detections, not proposals")
     if (args.predictions is None) == (args.config_file is None):
         raise SystemExit("give either --predictions (score a saved file) or --config-file with --output-dir (evaluate, then score)")
     if args.config_file is not None:
@@ -152,6 +202,8 @@ def main():
                                    else args.voc_iou, use_07_metric=args.metric != "voc12")
         for iou, row in zip(args.voc_iou, result.get("ap_by_iou", ())):
             log.info("IoU %.2f: mAP %.4f", iou, float(row[row == row].mean()) if (row == row).any() else float("nan"))
+        if args.errors:
+            _error_tables(args, dataset, predictions, folder, log)
         return
     expected = [(task, metric, (float(mean), float(std))) for task, metric, mean, std in args.expected]
     out = evaluate(dataset, predictions, folder, box_only=args.proposals,
@@ -160,6 +212,8 @@ def main():
         results, records = out
         log.info("%d detections on %d images", len(records["bbox"]), len(dataset))
         log.info("COCO box AP (rows: all categories, then each json category id)\n%s", results.table())
+    if args.errors and not args.proposals:
+        _error_tables(args, dataset, predictions, folder, log)
 
 
 if __name__ == "__main__":
